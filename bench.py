@@ -2,7 +2,15 @@
 """Headline benchmark: env-steps/s of the batched hedging env on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--envs E]
-                    [--mode rollout|graph|eager]
+                    [--mode rollout|graph|eager] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints one JSON line (value,
+ms_per_step, ...; the roofline where the timed region itself gives the kernel's time).
+`--dump-outputs DIR` also writes what the last timed step returned as DIR/<name>.npy: the
+inputs are seeded and the env's state at the timed steps does not depend on the clock, so
+two builds can be compared array for array.  `--full` adds every other leg: the rocprofv3
+PMC passes, the CPU baseline, the per-dispatch kernel probe, the Gym-API step line, the
+host-API and closed-loop policy timings and the shard check.
 
 Workload = BASELINE.json configs[1]: 65,536 parallel envs per GPU, GBM price
 advance (Philox4x32-10 normals), Black-Scholes rolling-ATM marks, v2 env with
@@ -15,14 +23,14 @@ Modes: `rollout` (default) fuses 64 steps per launch (he_rollout: actions
 [64,N,2] in, obs [64,N,13] / reward / terminated out, the collect_rollouts
 inner loop of train_ppo_v2.py:48 with actions supplied up front); `graph`
 replays he_step launches captured into hipGraphs, one kernel per step (the
-Gym step API path); `eager` calls he_step from Python every step.  At N=1 the
-JSON line also carries the graph-mode he_step measurement under "step_api".
+Gym step API path); `eager` calls he_step from Python every step.  At N=1 with
+--full the JSON line also carries the graph-mode he_step measurement under "step_api".
 For N>1 the script runs under torch.distributed.run, one rank per GPU (weak
 scaling: E envs per rank, env ids offset by rank), and all-gathers the per-env
 episode summaries {return, sum P&L, sum cost, length} (he_episode_summaries) over
 RCCL every 256 steps (the rollout-buffer boundary of train_ppo_v2.py:48).
 `--gpus N` without WORLD_SIZE in the environment makes this process the launcher:
-it runs the PMC pass and the CPU baseline (no GPU call of its own: the PMC pass is a
+with --full it runs the PMC pass and the CPU baseline (no GPU call of its own: the PMC pass is a
 rocprofv3 child), then starts `python -m torch.distributed.run --nproc-per-node N
 bench.py ...` as a child process and exits with its status; rank 0 merges the
 launcher's results into its JSON line.
@@ -103,7 +111,7 @@ def tile_layout(mode, n):
 
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s
-# >= 2 episodes of 252 steps; 25,600 = 100 launches of the K = 256 rollout, so
+# The default --steps: >= 2 episodes of 252 steps; 25,600 = 100 launches of the K = 256 rollout, so
 # the timed region's per-launch device time averages over 100 dispatches (~30 ms at config 2:
 # over 10 the same box read 292 and 318 us in two processes, r03s34)
 MIN_TIMED_STEPS = 25600
@@ -187,7 +195,7 @@ def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None,
-                    help=f"env: timed env-steps (default and floor {MIN_TIMED_STEPS}); rbergomi: launches (default 5)")
+                    help=f"env: timed env-steps, exactly (default {MIN_TIMED_STEPS}); rbergomi: launches (default 5)")
     ap.add_argument("--warmup", type=int, default=None, help="env: default 256; rbergomi: default 1")
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS), help="BASELINE.json config")
     ap.add_argument("--envs", type=int, default=None, help="envs per GPU (default: the config's)")
@@ -195,6 +203,13 @@ def parse(argv=None):
     ap.add_argument("--rollout-k", type=int, default=None,
                     help="steps per he_rollout call (default: 256, the n_steps rollout-buffer boundary of "
                          "train_ppo_v2.py:48, on the LDS path; 64 on the tile path)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the rocprofv3 PMC passes, the CPU baseline, the per-dispatch "
+                         "kernel probe, the Gym-API (graph-mode he_step) line, the host-API and closed-loop policy "
+                         "timings and the shard check (the --no-* options below drop single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as "
+                         "DIR/<name>.npy (f32 / f64; see dump_outputs)")
     ap.add_argument("--no-step-api", action="store_true", help="skip the secondary graph-mode he_step run")
     ap.add_argument("--no-sb3-api", action="store_true", help="skip the host-API (SB3 VecEnv / single env) timing")
     ap.add_argument("--no-policy-api", action="store_true",
@@ -217,6 +232,10 @@ def parse(argv=None):
                     help="N > 1: also all-gather each boundary's rollout tensors (obs / reward / terminated of "
                          "the last he_rollout) in global env order (SURVEY 8(e): small N only)")
     args = ap.parse_args(argv)
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must be >= 0")
     if args.workload == "env":
         args.steps = MIN_TIMED_STEPS if args.steps is None else args.steps
         args.warmup = 256 if args.warmup is None else args.warmup
@@ -445,6 +464,8 @@ class Runner:
             self.rt = torch.empty((RK, n), dtype=torch.uint8, device=dev)
         self.graphs = []
         self.replays = 0
+        self.tail = 0       # graph mode: he_step calls made past the last whole block
+        self.last_k = 0     # steps of the most recent launch (rollout: rows of ro / rr / rt it wrote)
         self.runs = []
         if mode == "graph":
             with torch.cuda.stream(stream):
@@ -471,8 +492,10 @@ class Runner:
         if st:
             raise RuntimeError(self.lib.he_last_error(self.h).decode())
 
-    def rollout(self, done, s):
-        RK = self.args.rollout_k
+    def rollout(self, done, s, k=None):
+        """One he_rollout of k steps (default: the chunk, --rollout-k) into the first k rows of
+        the output buffers."""
+        RK = self.args.rollout_k if k is None else k
         a0 = done % self.ring
         acts = self.sets[self.launches % self.sets.shape[0]]
         self.launches += 1
@@ -483,11 +506,24 @@ class Runner:
             raise RuntimeError(self.lib.he_last_error(self.h).decode())
 
     def run(self, steps):
-        """Enqueue `steps` env-steps (a multiple of the chunk) on self.stream."""
+        """Enqueue exactly `steps` env-steps on self.stream: whole chunks, then the remainder
+        (rollout: one shorter he_rollout; graph: he_step calls outside the graphs, see realign)."""
         self.runs.append(steps)   # the call sequence, replayed by the shard check
         done = 0
         cs = self.stream.cuda_stream
         while done < steps:
+            if steps - done < self.chunk:
+                rest = steps - done
+                if self.mode == "rollout":
+                    self.rollout(done, cs, rest)
+                else:
+                    base = (self.replays % len(self.graphs)) * M_BLOCK
+                    for j in range(rest):
+                        self.step(base + j, cs)
+                    self.tail = rest
+                self.last_k = rest
+                break
+            self.last_k = self.chunk
             if self.mode == "graph":
                 self.graphs[self.replays % len(self.graphs)].replay()
                 self.replays += 1
@@ -498,6 +534,21 @@ class Runner:
             done += self.chunk
             if self.dist is not None and done % GATHER_EVERY == 0:
                 self.gather(cs)
+
+    def realign(self):
+        """Graph mode, after a run() that ended inside a market block: the rest of that block's
+        he_step calls (untimed), so that the next graph replay starts at a block boundary as
+        the captured launches assume."""
+        if not self.tail:
+            return
+        base = (self.replays % len(self.graphs)) * M_BLOCK
+        with torch.cuda.stream(self.stream):
+            for j in range(self.tail, M_BLOCK):
+                self.step(base + j, self.stream.cuda_stream)
+            self.env.sync_market()
+        torch.cuda.synchronize()
+        self.replays += 1
+        self.tail = 0
 
     def gather(self, cs):
         """The rollout-buffer boundary (train_ppo_v2.py:48, n_steps = 256): every rank's
@@ -821,35 +872,90 @@ def market_time_ms(hev, args, dev, acts, stream):
 
 # The GPU's clocks ramp up under sustained load: back-to-back 65,536-env launches measured
 # 395-404 us each in the first ~10 ms after idle and 320 us from ~30 ms on
-# (tools/launch_timing.py, r03s2).  The warm-up therefore runs for at least this long
-# (whole chunks; the line reports the warm-up steps actually run beside the requested ones).
+# (tools/launch_timing.py, r03s2).  The GPU is therefore kept busy for at least this long
+# before the timed steps (whole chunks; see timed()).
 MIN_WARMUP_SECONDS = 0.5
 
 
-def timed(runner, K, W, dist):
-    """W untimed warm-up steps (extended to MIN_WARMUP_SECONDS of work; the count run is left
-    in runner.warmup_steps), then exactly K timed steps between barriers; returns
-    (max-over-ranks wall seconds, device ms on the stream)."""
+# --dump-outputs: 64 MB in all at the most.  Per-env arrays of the last step (16 f32 per env)
+# are written whole up to DUMP_MAX_ENVS envs, beyond that for a seeded sample of the envs; the
+# last launch's whole [k, ...] tensors for DUMP_LAUNCH_ENVS sampled envs (256 x 256 x 15 f32 = 3.9 MB).
+DUMP_MAX_ENVS = 750000
+DUMP_LAUNCH_ENVS = 256
+
+
+def env_outputs(runner, seed):
+    """What the caller of the timed path holds after its last timed launch, {name: tensor}.
+    rollout: he_rollout's obs / reward / terminated rows of the launch's last step ([n, 13],
+    [n], [n]) and, for a sample of the envs, of every step of that launch (`launch_*`
+    [k, m, ...]); graph / eager: he_step's obs / reward / terminated / truncated.  The env
+    samples come from default_rng(seed), sorted, the same in every run."""
+    n = runner.args.envs
+    rng = np.random.default_rng(seed)
+    dev = runner.acts.device
+    rows = None
+    if n > DUMP_MAX_ENVS:
+        rows = torch.from_numpy(np.sort(rng.choice(n, DUMP_MAX_ENVS, replace=False))).to(dev)
+    pick = (lambda t: t) if rows is None else (lambda t: t.index_select(0, rows))
+    if runner.mode != "rollout":
+        e = runner.env
+        return dict(obs=pick(e._obs), reward=pick(e._rew), terminated=pick(e._term), truncated=pick(e._trunc))
+    k = runner.last_k
+    sample = torch.from_numpy(np.sort(rng.choice(n, min(n, DUMP_LAUNCH_ENVS), replace=False))).to(dev)
+    ro, rr, rt = runner.ro, runner.rr, runner.rt
+    return dict(obs=pick(ro[k - 1]), reward=pick(rr[k - 1]), terminated=pick(rt[k - 1]),
+                launch_obs=ro[:k].index_select(1, sample), launch_reward=rr[:k].index_select(1, sample),
+                launch_terminated=rt[:k].index_select(1, sample))
+
+
+def dump_outputs(path, tensors, rank=0, world=1):
+    """Write {name: tensor} as path/<name>.npy (ranks > 1: <name>_rank<r>.npy); f64 stays f64,
+    every other dtype is written as f32."""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, t in tensors.items():
+        a = t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + ("_rank%d" % rank if world > 1 else "") + ".npy"), np.ascontiguousarray(a))
+
+
+def timed(runner, K, W, dist, warm=None):
+    """W untimed warm-up steps, then exactly K timed steps between barriers; returns
+    (max-over-ranks wall seconds, device ms on the stream).  The GPU is kept busy for at least
+    MIN_WARMUP_SECONDS before the timed steps.  With `warm` (a second Runner of the same
+    launches on a handle of its own, sharing `runner`'s stream) the extra launches run there,
+    first, and `runner` takes exactly W steps: its state at the timed steps, and so what they
+    compute, is the same in every run.  Without it they run on `runner` after the W steps (the
+    count run is left in runner.warmup_steps)."""
     stream = runner.stream
     t_w = time.perf_counter()
     d_saved, runner.dist = runner.dist, None  # no gathers while warming: ranks' counts may differ
-    with torch.cuda.stream(stream):
-        runner.run(W)
-    torch.cuda.synchronize()
-    while time.perf_counter() - t_w < MIN_WARMUP_SECONDS:
-        with torch.cuda.stream(stream):
-            runner.run(runner.chunk * 4)
-        torch.cuda.synchronize()
-        W += runner.chunk * 4
-    if dist is not None:  # every rank warms for the longest rank's count of steps
-        w = torch.tensor([W], dtype=torch.int64,
-                         device="cpu" if dist.get_backend() == "gloo" else torch.device("cuda", torch.cuda.current_device()))
-        dist.all_reduce(w, op=dist.ReduceOp.MAX)
-        if int(w.item()) > W:
+    if warm is not None:
+        while time.perf_counter() - t_w < MIN_WARMUP_SECONDS:
             with torch.cuda.stream(stream):
-                runner.run(int(w.item()) - W)
+                warm.run(warm.chunk * 4)
             torch.cuda.synchronize()
-            W = int(w.item())
+        if W:
+            with torch.cuda.stream(stream):
+                runner.run(W)
+            torch.cuda.synchronize()
+    else:
+        with torch.cuda.stream(stream):
+            runner.run(W)
+        torch.cuda.synchronize()
+        while time.perf_counter() - t_w < MIN_WARMUP_SECONDS:
+            with torch.cuda.stream(stream):
+                runner.run(runner.chunk * 4)
+            torch.cuda.synchronize()
+            W += runner.chunk * 4
+        if dist is not None:  # every rank warms for the longest rank's count of steps
+            w = torch.tensor([W], dtype=torch.int64,
+                             device="cpu" if dist.get_backend() == "gloo" else torch.device("cuda", torch.cuda.current_device()))
+            dist.all_reduce(w, op=dist.ReduceOp.MAX)
+            if int(w.item()) > W:
+                with torch.cuda.stream(stream):
+                    runner.run(int(w.item()) - W)
+                torch.cuda.synchronize()
+                W = int(w.item())
     runner.dist = d_saved
     runner.boundary_events = []   # the timed region's boundaries only
     if dist is not None:
@@ -1307,13 +1413,13 @@ def rbergomi_main(args):
     base = rb.estimate_base_params(hist)
     cpu = None
     valu, traffic = (None, "skipped"), (None, "skipped")
-    if world == 1 and not args.probe and not args.no_pmc:
+    if world == 1 and args.full and not args.probe and not args.no_pmc:
         # counters of mc_kernel in rocprofv3 children (before this process touches the GPU)
         pa = ["--workload", "rbergomi", "--rb-paths", str(args.rb_paths), "--rb-normals", args.rb_normals]
         res, err = pmc_pass(args, VALU_COUNTERS, "mc_kernel", probe_argv=pa)
         valu = (valu_summary(res).get("mc_kernel"), None) if res else (None, err)
         traffic = pmc_traffic(args, "mc_kernel", pa)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.probe:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.probe:
         cpu = rb_cpu_baseline(args.cpu_seconds, base)
     dist = None
     if world > 1:
@@ -1369,6 +1475,12 @@ def rbergomi_main(args):
     if dist is not None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall = float(t.item())
+    if args.dump_outputs:
+        # the last launch's marks [P, 252] f64; past 12,000 paths (48 MB) a seeded sample of the paths
+        rows = (torch.arange(P, device=dev) if P <= 12000 else torch.from_numpy(
+            np.sort(np.random.default_rng(args.seed).choice(P, 12000, replace=False))).to(dev))
+        dump_outputs(args.dump_outputs, dict(call=call.index_select(0, rows), put=put.index_select(0, rows)),
+                     rank, world)
     n_opt = P * RB_DAYS * 2
     if rank == 0:
         line = {
@@ -1425,7 +1537,7 @@ def launch(args, argv):
     import subprocess
     import tempfile
     parent = dict(pmc=None, pmc_note="skipped", cpu_baseline=None)
-    if not args.launch_dry_run:
+    if args.full and not args.launch_dry_run:
         if args.workload == "env" and not args.no_pmc:
             t, v = pmc_traffic(args)
             parent.update(pmc=t, pmc_note=v if t is None else None, pmc_counters=v if t is not None else None)
@@ -1538,7 +1650,7 @@ def main(argv=None):
         pmc = (parent["pmc"], parent.get("pmc_counters") or parent.get("pmc_note"))
         valu = (parent.get("valu"), parent.get("valu_note"))
         cpu = parent["cpu_baseline"]
-    elif world == 1:
+    elif world == 1 and args.full:
         if not args.no_pmc:
             pmc = pmc_traffic(args)
             # the instruction-issue side: the LDS kernel makes the market on chip, so every
@@ -1569,14 +1681,25 @@ def main(argv=None):
     env = make_env(args, dev, rank)
     runner = Runner(args, env, args.mode, acts, stream, dist, gathered)
     acts = runner.acts   # [256, n, 2]: set 0 (the other legs below use one set)
-    # at least two full episodes (504 steps) in the timed window
-    K = -(-max(args.steps, MIN_TIMED_STEPS) // runner.chunk) * runner.chunk
+    # --steps timed steps, exactly (default MIN_TIMED_STEPS; SURVEY 8(d) asks for at least two
+    # full episodes, 504 steps, in the timed window); the warm-up in whole launches
+    K = args.steps
     W = -(-args.warmup // runner.chunk) * runner.chunk
-    rank_phase("env made; warmup %d + timed %d steps" % (W, K))
-    wall, dev_ms = timed(runner, K, W, dist)
-    rank_phase("timed region done")
-    shard = None
+    # the launches that bring the clocks up run on a handle of their own (the same launches into
+    # the same output buffers), so the timed steps start from the same state in every run
+    warm_env = make_env(args, dev, rank)
+    warm = Runner(args, warm_env, args.mode, runner.sets, stream)
     if args.mode == "rollout":
+        warm.ro, warm.rr, warm.rt = runner.ro, runner.rr, runner.rt
+    rank_phase("env made; warmup %d + timed %d steps" % (W, K))
+    wall, dev_ms = timed(runner, K, W, dist, warm)
+    rank_phase("timed region done")
+    warm_env.close()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, env_outputs(runner, args.seed), rank, world)
+    runner.realign()
+    shard = None
+    if args.mode == "rollout" and args.full:
         # every env's summaries after the last launch, gathered in global env order (outside
         # the timed region), then each rank's re-run of its neighbour's last envs
         with torch.cuda.stream(stream):
@@ -1610,7 +1733,7 @@ def main(argv=None):
                      "env_dim=1)", shapes=[list(ro.shape), list(rr.shape), list(rt.shape)],
                 bytes_per_rank=int(sum(t.numel() * t.element_size() for t in (ro, rr, rt)) // world))
     hev = HipEvents()
-    probe_ms = kernel_time_ms(hev, runner, 64 if args.mode == "rollout" else 256)
+    probe_ms = kernel_time_ms(hev, runner, 64 if args.mode == "rollout" else 256) if args.full else None
     env.close()
     # The dominant kernel's average launch duration.  On the LDS path one he_rollout is one
     # lds_rollout_kernel dispatch, so the HIP events around the timed region on the
@@ -1618,7 +1741,7 @@ def main(argv=None):
     # rank nothing else runs on the stream).  Elsewhere (tile path: market + step kernels
     # per call; ranks > 1: the gathers ride on the stream) the per-dispatch probe
     # (he_time_next_step: hipExtLaunchKernelGGL events around exactly the step kernel).
-    launches = K // runner.chunk
+    launches = K / runner.chunk   # whole launches, but for a --steps that is no multiple of the chunk
     region = (lds or (replay and args.mode == "rollout")) and world == 1
     kern_ms = dev_ms / launches if region else probe_ms
     per_rank = None
@@ -1627,7 +1750,7 @@ def main(argv=None):
         # per-dispatch probe, the device time per launch over the timed region (kernels +
         # the boundaries riding on the stream), and the boundary's device time
         b_us, r_us = runner.boundary_us()
-        mine = torch.tensor([rank, probe_ms * 1e3, dev_ms / launches * 1e3,
+        mine = torch.tensor([rank, probe_ms * 1e3 if probe_ms is not None else float("nan"), dev_ms / launches * 1e3,
                              b_us if b_us is not None else float("nan"), r_us if r_us is not None else float("nan"),
                              runner.gathers, wall], dtype=torch.float64,
                             device="cpu" if backend == "gloo" else dev)
@@ -1636,29 +1759,34 @@ def main(argv=None):
         per_rank = []
         for v in allv:
             v = v.cpu().tolist()
-            per_rank.append(dict(rank=int(v[0]), kernel_us_probe=round(v[1], 3), device_us_per_launch=round(v[2], 3),
+            per_rank.append(dict(rank=int(v[0]), kernel_us_probe=None if v[1] != v[1] else round(v[1], 3),
+                                 device_us_per_launch=round(v[2], 3),
                                  boundary_us=None if v[3] != v[3] else round(v[3], 2),
                                  rollout_gather_us=None if v[4] != v[4] else round(v[4], 2),
                                  boundaries=int(v[5]), wall_s=round(v[6], 6)))
 
-    roof = roofline(args.mode, n, kern_ms, args.rollout_k, has_book, tile_layout(cfg["mode"], n), lds)
-    roof["kernel_us_source"] = ("HIP events around the timed region / %d launches" % launches if region else
-                                "he_time_next_step probe: HIP events around single dispatches")
-    roof["kernel_us_probe"] = round(probe_ms * 1e3, 3)
-    roof["kernel_us_timed_region"] = round(dev_ms / launches * 1e3, 3)
-    if not lds and not replay:  # the tile path: market_kernel makes the HBM market tile
-        roof["tile_layout"] = tile_layout(cfg["mode"], n)
-        mkt_ms = market_time_ms(hev, args, dev, acts, stream)
-        roof["market_kernel_us_per_64_steps"] = round(mkt_ms * 1e3, 3)
-        roof["market_kernel_us_per_step"] = round(mkt_ms * 1e3 / M_BLOCK, 3)
-        steps_per_launch = args.rollout_k if args.mode == "rollout" else 1
-        if mkt_ms / M_BLOCK > kern_ms / steps_per_launch:
-            roof["dominant_kernel"] = "market_kernel (the HBM market tile, %.1f us per step vs %.1f for the steps)" % (
-                mkt_ms * 1e3 / M_BLOCK, kern_ms * 1e3 / steps_per_launch)
-    roof = finish_roofline(roof, cfg, valu, pmc, kern_ms)
+    # Without --full the roofline is there only where the timed region itself gives the kernel's
+    # time; the probe, the market kernel's timing and the PMC figures are runs of their own.
+    roof = None
+    if kern_ms is not None:
+        roof = roofline(args.mode, n, kern_ms, args.rollout_k, has_book, tile_layout(cfg["mode"], n), lds)
+        roof["kernel_us_source"] = ("HIP events around the timed region / %g launches" % launches if region else
+                                    "he_time_next_step probe: HIP events around single dispatches")
+        roof["kernel_us_probe"] = round(probe_ms * 1e3, 3) if probe_ms is not None else None
+        roof["kernel_us_timed_region"] = round(dev_ms / launches * 1e3, 3)
+        if args.full and not lds and not replay:  # the tile path: market_kernel makes the HBM market tile
+            roof["tile_layout"] = tile_layout(cfg["mode"], n)
+            mkt_ms = market_time_ms(hev, args, dev, acts, stream)
+            roof["market_kernel_us_per_64_steps"] = round(mkt_ms * 1e3, 3)
+            roof["market_kernel_us_per_step"] = round(mkt_ms * 1e3 / M_BLOCK, 3)
+            steps_per_launch = args.rollout_k if args.mode == "rollout" else 1
+            if mkt_ms / M_BLOCK > kern_ms / steps_per_launch:
+                roof["dominant_kernel"] = ("market_kernel (the HBM market tile, %.1f us per step vs %.1f for the "
+                                           "steps)" % (mkt_ms * 1e3 / M_BLOCK, kern_ms * 1e3 / steps_per_launch))
+        roof = finish_roofline(roof, cfg, valu, pmc, kern_ms)
 
     step_api = None
-    if world == 1 and args.mode != "graph" and not args.no_step_api:
+    if world == 1 and args.full and args.mode != "graph" and not args.no_step_api:
         # secondary: the Gym step API path, one he_step launch per step in hipGraphs
         env_g = make_env(args, dev)
         rg = Runner(args, env_g, "graph", acts, stream)
@@ -1670,10 +1798,10 @@ def main(argv=None):
         step_api = step_api_line(n, Kg, wall_g, rf, step_pmc, tile_layout(cfg["mode"], n))
 
     sb3 = None
-    if world == 1 and args.config == 2 and not args.no_sb3_api:
+    if world == 1 and args.full and args.config == 2 and not args.no_sb3_api:
         sb3 = sb3_api(dev)
     pol = None
-    if world == 1 and args.mode == "rollout" and not args.no_policy_api:
+    if world == 1 and args.full and args.mode == "rollout" and not args.no_policy_api:
         pol = policy_api(args, dev, args.rollout_k, kern_ms * 1e3)
 
     if rank == 0:
@@ -1684,8 +1812,8 @@ def main(argv=None):
             "n_gpus": world,
             "steps": K,
             "warmup": runner.warmup_steps,
-            # the command's --steps / --warmup: raised to the timed floor (MIN_TIMED_STEPS, >= 2
-            # episodes and 100 launches) and to whole launches of the rollout chunk
+            # the command's --steps / --warmup: the timed steps are exactly --steps, the warm-up
+            # is raised to whole launches of the chunk
             "requested_steps": args.steps,
             "requested_warmup": args.warmup,
             "ms_per_step": round(wall * 1e3 / K, 6),

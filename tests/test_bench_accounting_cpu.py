@@ -21,6 +21,15 @@ def bench():
     return mod
 
 
+def test_plain_run_is_the_default_and_steps_are_taken_as_given(bench):
+    a = bench.parse(["--gpus", "1", "--steps", "10", "--warmup", "3"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (10, 3, False, None)
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (bench.MIN_TIMED_STEPS, 256, True, "out")
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
 def test_threshold_matches_library(bench):
     src = open(os.path.join(REPO, "cantorrl_amd", "csrc", "hedge_env.hip")).read()
     assert f"constexpr int64_t kGreeksInStepMinEnvs = {bench.GREEKS_IN_STEP_MIN_ENVS};" in src

@@ -23,7 +23,7 @@ d=[json.loads(l) for l in open(sys.argv[1]) if l.startswith('{')][0]; print(sys.
   done
 done
 if [ -n "$HEADLINE" ]; then
-  timeout -k 10 400 python -u bench.py --no-cpu-baseline > $O/bench2.log 2>&1 || { tail -5 $O/bench2.log; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --no-cpu-baseline > $O/bench2.log 2>&1 || { tail -5 $O/bench2.log; exit 1; }
   grep "^{" $O/bench2.log > $O/bench2.jsonl
   python3 -c "
 import json

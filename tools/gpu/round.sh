@@ -40,8 +40,8 @@ if [ "$PHASE" = extra ]; then
   echo "[$(date +%T)] done"
   exit 0
 fi
-echo "[$(date +%T)] bench (default: PMC + CPU baseline + step API)"
-timeout -k 10 400 python -u bench.py > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
+echo "[$(date +%T)] bench --full (PMC + CPU baseline + step API)"
+timeout -k 10 400 python -u bench.py --full > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
 grep "^{" $O/bench.log > $O/bench.jsonl
 echo "[$(date +%T)] bench under rocprofv3 --kernel-trace --stats"
 cd /tmp
@@ -59,11 +59,11 @@ for c in 3 4 5 6; do
   # configs 4, 5 (book / Heston: producer-bound) and 6 (replay) with the PMC passes: traffic + VALU issue
   pmc=--no-pmc; [ $c != 3 ] && pmc=""
   sapi=--no-step-api; [ $c = 3 ] && sapi=""   # config 3: the Gym-API he_step line at 1M envs
-  timeout -k 10 400 python -u bench.py --config $c $pmc $sapi --no-cpu-baseline > $O/b_cfg$c.log 2>&1 || { tail -20 $O/b_cfg$c.log; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --config $c $pmc $sapi --no-cpu-baseline > $O/b_cfg$c.log 2>&1 || { tail -20 $O/b_cfg$c.log; exit 1; }
   grep "^{" $O/b_cfg$c.log >> $O/bench_cfg345.jsonl
 done
 echo "[$(date +%T)] --gpus 2 rehearsal (gloo, one GPU)"
-BENCH_DIST_BACKEND=gloo timeout -k 10 300 python -u bench.py --gpus 2 --no-pmc --no-cpu-baseline --no-step-api --steps 512 --warmup 256 > $O/b_gpus2.log 2>&1 || { tail -30 $O/b_gpus2.log; exit 1; }
+BENCH_DIST_BACKEND=gloo timeout -k 10 300 python -u bench.py --gpus 2 --full --no-pmc --no-cpu-baseline --no-step-api --steps 512 --warmup 256 > $O/b_gpus2.log 2>&1 || { tail -30 $O/b_gpus2.log; exit 1; }
 grep "^{" $O/b_gpus2.log > $O/bench_gpus2_rehearsal.jsonl
 python3 - <<PY
 import json
