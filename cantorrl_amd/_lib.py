@@ -122,7 +122,7 @@ EXPORTS = [
     "he_sync_market", "he_vecnorm_stats_len", "he_vecnorm_scratch_bytes", "he_vecnorm_init", "he_vecnorm_step",
     "he_vecnorm_apply", "he_vecnorm_attach", "he_vecnorm_attach_eval", "he_vecnorm_reset", "he_fixed_european_marks", "he_bs_delta_hedge", "he_count_nonfinite",
     "he_device_rng", "he_device_math", "he_host_math", "he_episode_summaries", "he_host_alloc", "he_host_free",
-    "he_stream_wait", "he_step_signal", "he_signal_seq", "he_signal_wait",
+    "he_stream_wait", "he_step_signal", "he_signal_seq", "he_signal_wait", "he_host_episode_wrap",
 ]
 
 
@@ -210,6 +210,7 @@ def load(path=LIB_PATH):
         "he_device_rng": (i32, [u64, vp, vp, i64, vp, vp, vp]),
         "he_device_math": (i32, [i32, vp, i64, vp, vp]),
         "he_host_math": (i32, [i32, vp, i64, vp]),
+        "he_host_episode_wrap": (i32, [vp, vp, vp, i64, i32, vp]),
         "he_episode_summaries": (i32, [vp, vp, vp]),
         "he_host_alloc": (i32, [ctypes.c_size_t, ctypes.POINTER(vp), ctypes.POINTER(vp)]),
         "he_host_free": (i32, [vp]),

@@ -213,6 +213,18 @@ HE_HD int32_t trade_round(float f, int32_t mt) {
 #endif
 }
 
+// Episode-step wrap (t + k) % T for t < T (t + k < 2^32) without the integer division where
+// one subtraction does: k <= T leaves t + k < 2 T.  episode_wrap_le is that form alone, for
+// callers that hold k <= T (the LDS kernels: T >= the block length); episode_wrap tests k
+// against T (a uniform branch where both are) and keeps the modulo for k > T.
+HE_HD uint32_t episode_wrap_le(uint32_t t, uint32_t k, uint32_t T) {
+    const uint32_t s = t + k;
+    return s >= T ? s - T : s;
+}
+HE_HD uint32_t episode_wrap(uint32_t t, uint32_t k, uint32_t T) {
+    return k <= T ? episode_wrap_le(t, k, T) : (t + k) % T;
+}
+
 // ---------------------------------------------------------------- Philox4x32-10
 // Salmon et al. (SC'11) / Random123; same block function as rocRAND's
 // philox4x32_10.  Counter = (lo(n), hi(n), lo(g), hi(g)), key = (lo(seed), hi(seed)).

@@ -2221,7 +2221,7 @@ __device__ __forceinline__ void flush_obs_full(const float* img, float* out, int
 // tracks and the obs greeks it re-evaluates from the slot's market; no action crosses the waves,
 // and the LDS block pipeline is the stored-action rollout's.  The reward stepper keeps the
 // evaluation loops' episode sums and records (step_body's POL), the obs stepper stores the actions.
-template <int MODE, bool BOOK, bool LEAN, bool OBS, bool POL = false>
+template <int MODE, bool BOOK, bool LEAN, bool OBS, bool POL = false, bool PLAIN_OK = false>
 __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& io, int k_steps, const Market& cur,
                                             LdsMarketT<MODE, BOOK, LEAN>& L, int64_t base) {
     constexpr int D = kLdsPrefetch;
@@ -2383,6 +2383,14 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
 
     // ---- the block loop over a step function step(buf, sl, k, action, in_full_block)
     constexpr int NB = LdsMarketT<MODE, BOOK, LEAN>::NB;
+    // PLAIN (the lean steppers of stored-action rollouts): a full block in which no lane of the
+    // wave ends an episode (e.t + kLdsM < T for all) runs a second instance of the same slots
+    // with the episode handling compiled out -- every select's no-boundary arm, so the same
+    // bits; the same loads and stores in the same order, so the same counts in flight where the
+    // two bodies merge.  One ballot and one scalar branch per block, outside the unrolled slots.
+    // Both steppers and the producers make the test from their own counters of the same episode
+    // steps.  Envs reset apart (lanes at different episode steps) mostly take the general body.
+    constexpr bool kPlain = PLAIN_OK && LEAN && !POL;
     auto run_blk = [&](auto&& step) {
         LDS_BAR();  // block 0 produced
         for (int b = 0; b < nfull; ++b) {
@@ -2391,15 +2399,23 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
             continue;
 #endif
             const int buf = b % NB;
+            auto slots = [&](auto plain) {
 #pragma unroll
-            for (int sl = 0; sl < kLdsM; ++sl) {
-                const int k = b * kLdsM + sl;
-                const float2 ak = ra[sl % D];
-                if constexpr (!POL) {
-                    const int kn = k + D;
-                    ra[sl % D] = ld2(gact, (int64_t)(kn < k_steps ? kn : k_steps - 1) * N + i);
+                for (int sl = 0; sl < kLdsM; ++sl) {
+                    const int k = b * kLdsM + sl;
+                    const float2 ak = ra[sl % D];
+                    if constexpr (!POL) {
+                        const int kn = k + D;
+                        ra[sl % D] = ld2(gact, (int64_t)(kn < k_steps ? kn : k_steps - 1) * N + i);
+                    }
+                    step(buf, sl, k, ak, std::true_type{}, plain);
                 }
-                step(buf, sl, k, ak, std::true_type{});
+            };
+            if constexpr (kPlain) {
+                if (__ballot((int32_t)(e.t + (uint32_t)kLdsM) >= p.T) == 0ull) slots(std::true_type{});
+                else slots(std::false_type{});
+            } else {
+                slots(std::false_type{});
             }
             LDS_BAR();  // buffer b % NB handed back, block b + 1 produced
         }
@@ -2408,7 +2424,8 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
             const int buf = nfull % NB;
             for (int sl = 0; sl < tail; ++sl) {
                 const int k = nfull * kLdsM + sl;
-                step(buf, sl, k, POL ? make_float2(0.0f, 0.0f) : ld2(gact, (int64_t)k * N + i), std::false_type{});
+                step(buf, sl, k, POL ? make_float2(0.0f, 0.0f) : ld2(gact, (int64_t)k * N + i), std::false_type{},
+                     std::false_type{});
             }
 #endif
             LDS_BAR();
@@ -2435,7 +2452,16 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
             float preV = rst.v;
             if (HESTON && e.t != 0) preV = (float)cur.v[i];
             const double s0s_d = p.s0s_d, inv_s0s_d = p.inv_s0s_d;
-            auto obs_step = [&](int buf, int sl, int k, float2 ak, auto full) {
+            // this lane's row of the two staging tiles, as LDS addresses held in registers (opaque):
+            // the 13 row writes take immediate offsets from them.  Left to the compiler the tiles'
+            // offset in LdsMarketT, past the 1,020 B that ds_write2_b32 encodes, is added to
+            // lane * 52 + 4 c again for every pair of columns: 7-8 v_add_u32 per step.
+            using lds_float = __attribute__((address_space(3))) float;
+            lds_float* row0 = (lds_float*)&L.stage[0][lane * kObs];
+            lds_float* row1 = (lds_float*)&L.stage[1][lane * kObs];
+            asm volatile("" : "+v"(row0), "+v"(row1));
+            auto obs_step = [&](int buf, int sl, int k, float2 ak, auto full, auto plain) {
+                constexpr bool PLAIN = decltype(plain)::value;   // no episode ends in this block
                 const float2 r0 = L.sc[buf][sl][lane];
                 const float rP = L.pp[buf][sl][lane];
                 const float vk = HESTON ? L.vv[HESTON ? buf : 0][HESTON ? sl : 0][lane] : var_f;
@@ -2458,7 +2484,7 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
                 const int32_t cc = clamp_pos(nc, maxh);
                 const int32_t qq = clamp_pos(nq, maxh);
                 const uint32_t t1 = e.t + 1;
-                const bool term = (int32_t)t1 >= T;
+                const bool term = !PLAIN && (int32_t)t1 >= T;
                 // make_obs<true> (hedging_env_v2.py:109-143) on the post-step state, or the
                 // reset obs on a terminal step (SB3 autoreset)
                 float o[kObs];
@@ -2488,15 +2514,18 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
                 // staged in LDS (two tiles, alternating by step: the next step's row writes
                 // do not wait behind this step's read-back) and stored as whole 16-B lines
                 float* const tile = L.stage[k & 1];
+                lds_float* const row = (k & 1) ? row1 : row0;
                 // the reset row over it only on a step that ends an episode (a wave-uniform branch:
                 // fixed-length episodes end together) instead of 13 selects every step (with the f32
                 // quotients 287.8 -> 286.5 us, r05s13_ab_obs_f32.txt)
 #pragma unroll
-                for (int c = 0; c < kObs; ++c) tile[lane * kObs + c] = o[c];
-                if (__ballot(term) != 0ull) {
-                    if (term) {
+                for (int c = 0; c < kObs; ++c) row[c] = o[c];
+                if constexpr (!PLAIN) {
+                    if (__ballot(term) != 0ull) {
+                        if (term) {
 #pragma unroll
-                        for (int c = 0; c < kObs; ++c) tile[lane * kObs + c] = ro[c];
+                            for (int c = 0; c < kObs; ++c) row[c] = ro[c];
+                        }
                     }
                 }
                 if (!POL || io.obs) {   // policy rollouts may return no obs (a kernel argument: uniform)
@@ -2517,9 +2546,13 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
                 if (HESTON) preV = term ? rst.v : vk;
             };
             if (wrows == kLdsEnvs)
-                run_blk([&](int buf, int sl, int k, float2 ak, auto) { obs_step(buf, sl, k, ak, std::true_type{}); });
+                run_blk([&](int buf, int sl, int k, float2 ak, auto, auto plain) {
+                    obs_step(buf, sl, k, ak, std::true_type{}, plain);
+                });
             else
-                run_blk([&](int buf, int sl, int k, float2 ak, auto) { obs_step(buf, sl, k, ak, std::false_type{}); });
+                run_blk([&](int buf, int sl, int k, float2 ak, auto, auto plain) {
+                    obs_step(buf, sl, k, ak, std::false_type{}, plain);
+                });
         } else {
             const double tcpc = p.tcpc, slip_frac = p.slip_frac, lam = p.lam, w = p.w, theta = p.theta;
             const double shares_d = p.shares_d, inv_shares = p.inv_shares, den = p.den, inv_den = p.inv_den;
@@ -2548,7 +2581,8 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
             // POL: the reset row's policy columns, and the obs greeks' constants
             const float rs3 = p.rstv[4 + 3], rs4 = p.rstv[4 + 4], rs7 = p.rstv[4 + 7], rs9 = p.rstv[4 + 9];
             const float gnd = p.g_num_drift, gis = p.g_inv_sst_f, gsf = p.g_sst_f;
-            run_blk([&](int buf, int sl, int k, float2 ak, auto) {
+            run_blk([&](int buf, int sl, int k, float2 ak, auto, auto plain) {
+                constexpr bool PLAIN = decltype(plain)::value;   // no episode ends in this block
                 const int64_t koff = (int64_t)k * N;
                 const float2 sc = L.sc[buf][sl][lane];
                 const float pP = L.pp[buf][sl][lane];
@@ -2570,7 +2604,7 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
                 const double cash = e.cash - tc;
                 // (iv)-(vi) advance, mark-to-market (:216-238)
                 const uint32_t t1 = e.t + 1;
-                const bool term = (int32_t)t1 >= T;
+                const bool term = !PLAIN && (int32_t)t1 >= T;
                 const double optv = (double)cc * C100 + (double)qq * P100;   // (cc C) 100 + (qq P) 100
                 double pv = ((double)(shares_f * sc.x) + optv) + cash;
                 if (BOOK) pv = pv + L.bk[buf][sl][lane];  // liability book (extension): after cash
@@ -2602,6 +2636,11 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
                     po4 = term ? rs4 : div_int_byf((float)qq, maxh_f, p.inv_maxh_f);
                     pcd = term ? rs7 : gx;
                     ppd = term ? rs9 : gz;
+                } else if constexpr (PLAIN) {   // account's sums with no episode end
+                    sm0 = sm0 + reward;
+                    sm1 = sm1 + pnl;
+                    sm2 = sm2 + tc;
+                    slen = slen + 1u;
                 } else {
                     account(reward, pnl, tc, term);
                 }
@@ -2688,9 +2727,9 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
             }
         };
         if (OBS && wrows == kLdsEnvs)
-            run_blk([&](int buf, int sl, int k, float2 ak, auto) { step(buf, sl, k, ak, std::true_type{}); });
+            run_blk([&](int buf, int sl, int k, float2 ak, auto, auto) { step(buf, sl, k, ak, std::true_type{}); });
         else
-            run_blk([&](int buf, int sl, int k, float2 ak, auto) { step(buf, sl, k, ak, std::false_type{}); });
+            run_blk([&](int buf, int sl, int k, float2 ak, auto, auto) { step(buf, sl, k, ak, std::false_type{}); });
     }
     LDS_T1(OBS ? 1 : 0);
     if (!OBS && i0 < N) {
@@ -2727,7 +2766,7 @@ __device__ __forceinline__ void prod_prio_toggle(bool up) {
 // Producer waves: block bp of 64 envs into LDS buffer bp & 1 while the steppers consume
 // block bp - 1.  pw = producer wave index (kLdsPEnvs envs each).  Lanes past the last
 // env mirror env N-1 like the steppers' (identical values, identical addresses).
-template <int MODE, bool BOOK, bool LEAN>
+template <int MODE, bool BOOK, bool LEAN, bool PLAIN_OK = false>
 __device__ __forceinline__ void lds_producer(const Params& p, int k_steps, const Market& cur,
                                              LdsMarketT<MODE, BOOK, LEAN>& W, int64_t base, int pw) {
     using G = LdsGeom<MODE, BOOK>;
@@ -2774,8 +2813,13 @@ __device__ __forceinline__ void lds_producer(const Params& p, int k_steps, const
             // one): the per-slot `len` tests are compile-time true, so each stage's slots
             // are straight-line code -- independent chains the wave can interleave, and
             // one materialisation of each polynomial constant per stage instead of per slot
-            auto block = [&](auto full) {
+            // PLAIN (LOCK blocks only): no lane of the wave meets an episode boundary in the
+            // block (1 <= tpb and tpb + kLdsM < T: no slot starts an episode, none ends one), so
+            // the autoreset of the price chain, its step counter and the lagged terminal marks
+            // are compiled out -- every select's no-boundary arm, the same bits
+            auto block = [&](auto full, auto plain) {
                 constexpr bool FULL = decltype(full)::value;
+                constexpr bool PLAIN = decltype(plain)::value;
                 // LOCK: the lean GBM producers of a whole block evaluate their kLdsH slots in
                 // lockstep (he_math.h *_n forms: the same operations per slot, so the same
                 // bits, as kLdsH interleaved chains with shared constants)
@@ -2783,7 +2827,7 @@ __device__ __forceinline__ void lds_producer(const Params& p, int k_steps, const
 
             const int64_t gid = p.goff + pi;
             const uint64_t nf = a0 + (uint64_t)(kb + sl0);
-            const uint32_t tpf = (tpb + (uint32_t)sl0) % T;
+            const uint32_t tpf = PLAIN ? 0u : episode_wrap(tpb, (uint32_t)sl0, T);
             double ex[kLdsH];   // own slots' growth factors S_j / S_{j-1} (before the clamp)
             double Vx[kLdsH];   // Heston: own slots' v after the step
             double Vin = Vbs;   // Heston: v before the lane's first slot
@@ -2928,14 +2972,14 @@ __device__ __forceinline__ void lds_producer(const Params& p, int k_steps, const
                 for (int j = 0; j < kLdsM; ++j) {
                     if (j == sl0) Sin = S;
                     if (FULL || j < len) {
-                        if (tp == 0) {  // autoreset: a new episode starts from S0
+                        if (!PLAIN && tp == 0) {  // autoreset: a new episode starts from S0
                             S = p.s0;
                             if (BOOK) Mr = p.s0;
                         }
                         const double Sn = S * eall[j];
                         S = (Sn < 1e-8) ? 1e-8 : Sn;  // np.maximum(., 1e-8), NaN kept
                         if (BOOK) Mr = np_max(Mr, S);   // market_body's barrier monitor
-                        tp = (tp + 1 == T) ? 0u : tp + 1;
+                        if (!PLAIN) tp = (tp + 1 == T) ? 0u : tp + 1;
                     }
 #pragma unroll
                     for (int h = 0; h < kLdsH; ++h) Sx[h] = (j == sl0 + h) ? S : Sx[h];
@@ -2957,11 +3001,15 @@ __device__ __forceinline__ void lds_producer(const Params& p, int k_steps, const
                 uint32_t tq = tpf;
 #pragma unroll
                 for (int h = 0; h < kLdsH; ++h) {
-                    const bool last = tq + 1 == T;
-                    const double Sprev = (h == 0) ? Sin : Sx[h - 1];
-                    Sm[h] = last ? ((tq == 0) ? p.s0 : Sprev) : Sx[h];
+                    if constexpr (PLAIN) {
+                        Sm[h] = Sx[h];
+                    } else {
+                        const bool last = tq + 1 == T;
+                        const double Sprev = (h == 0) ? Sin : Sx[h - 1];
+                        Sm[h] = last ? ((tq == 0) ? p.s0 : Sprev) : Sx[h];
+                        tq = (tq + 1 == T) ? 0u : tq + 1;
+                    }
                     Km[h] = rint(Sm[h]);   // marks<GBM>: the rolling-ATM strike K = round(S)
-                    tq = (tq + 1 == T) ? 0u : tq + 1;
                 }
                 bs_call_put_n<kLdsH>(Sm, Km, p.bs, lkC, lkP);
             }
@@ -3048,9 +3096,21 @@ __device__ __forceinline__ void lds_producer(const Params& p, int k_steps, const
                 }
             }
             };
-            if (len == kLdsM) block(std::true_type{});
-            else block(std::false_type{});
-            tpb = (uint32_t)(((uint64_t)tpb + kLdsM) % T);
+            if (len == kLdsM) {
+                // one wave-wide test per block, outside the unrolled slots (the generic producers
+                // -- Heston, a book, the non-lean marks -- keep the one body)
+                if constexpr (PLAIN_OK && LEAN && !HESTON && !BOOK) {
+                    if (__ballot(tpb == 0u || tpb + (uint32_t)kLdsM >= T) == 0ull)
+                        block(std::true_type{}, std::true_type{});
+                    else
+                        block(std::true_type{}, std::false_type{});
+                } else {
+                    block(std::true_type{}, std::false_type{});
+                }
+            } else {
+                block(std::false_type{}, std::false_type{});
+            }
+            tpb = episode_wrap(tpb, (uint32_t)kLdsM, T);
         }
         LDS_BAR();  // block bp handed to the steppers
     }
@@ -3140,6 +3200,10 @@ __device__ __forceinline__ int lds_role(int wave) {
 // and at 106 the 4 x 6 waves of 4 workgroups no longer fit a CU -- at 65,536 envs the
 // launch ran in two rounds of workgroups (536 vs ~270 us).  The spills go to VGPR lanes.
 constexpr int kLdsNumSgpr = 96;
+// Plain blocks (lds_stepper's run_blk, lds_producer's block) in the persistent-grid instances: the
+// producers take them; the steppers keep the one body -- with two, the GBM and the Heston lean
+// instances spill 14 / 16 VGPRs (60 / 68 B of scratch per lane) around the tile loop.
+constexpr bool kPlainPersistS = false, kPlainPersistP = true;
 template <int MODE, bool BOOK, bool LEAN, bool PERSIST = false, bool POL = false>
 __global__ __launch_bounds__((LdsGeom<MODE, BOOK>::threads), (LdsGeom<MODE, BOOK>::minwaves))
     __attribute__((amdgpu_num_sgpr(kLdsNumSgpr))) void lds_rollout_kernel(const Params* __restrict__ pc, State s, Io io,
@@ -3155,9 +3219,9 @@ __global__ __launch_bounds__((LdsGeom<MODE, BOOK>::threads), (LdsGeom<MODE, BOOK
     }
     if constexpr (!PERSIST) {   // one workgroup per 64-env tile
         const int64_t base = (int64_t)blockIdx.x * kLdsEnvs;
-        if (wave == 0) lds_stepper<MODE, BOOK, LEAN, false, POL>(p, s, io, k_steps, cur, lm, base);
-        else if (wave == 1) lds_stepper<MODE, BOOK, LEAN, true, POL>(p, s, io, k_steps, cur, lm, base);
-        else lds_producer<MODE, BOOK, LEAN>(p, k_steps, cur, lm, base, wave - 2);
+        if (wave == 0) lds_stepper<MODE, BOOK, LEAN, false, POL, true>(p, s, io, k_steps, cur, lm, base);
+        else if (wave == 1) lds_stepper<MODE, BOOK, LEAN, true, POL, true>(p, s, io, k_steps, cur, lm, base);
+        else lds_producer<MODE, BOOK, LEAN, true>(p, k_steps, cur, lm, base, wave - 2);
         return;
     }
     // PERSIST (launch_lds_rollout, more tiles than the device holds workgroups at once): a
@@ -3169,9 +3233,9 @@ __global__ __launch_bounds__((LdsGeom<MODE, BOOK>::threads), (LdsGeom<MODE, BOOK
         // (hoisted, the three roles' invariants all lived across the loop and spilled)
         asm volatile("" ::: "memory");
         const int64_t base = tile * kLdsEnvs;
-        if (wave == 0) lds_stepper<MODE, BOOK, LEAN, false, POL>(p, s, io, k_steps, cur, lm, base);
-        else if (wave == 1) lds_stepper<MODE, BOOK, LEAN, true, POL>(p, s, io, k_steps, cur, lm, base);
-        else lds_producer<MODE, BOOK, LEAN>(p, k_steps, cur, lm, base, wave - 2);
+        if (wave == 0) lds_stepper<MODE, BOOK, LEAN, false, POL, kPlainPersistS>(p, s, io, k_steps, cur, lm, base);
+        else if (wave == 1) lds_stepper<MODE, BOOK, LEAN, true, POL, kPlainPersistS>(p, s, io, k_steps, cur, lm, base);
+        else lds_producer<MODE, BOOK, LEAN, kPlainPersistP>(p, k_steps, cur, lm, base, wave - 2);
         if (tile + gridDim.x < tiles) __syncthreads();   // every role done with lm before the next tile
     }
 }
@@ -5050,6 +5114,14 @@ he_status he_host_math(int32_t op, const double* x, int64_t count, double* out) 
     if (op < 0 || op > 5 || count < 0 || (count > 0 && (!x || !out))) return HE_EINVAL;
     const BSConst bs = default_bs();
     for (int64_t g = 0; 4 * g < count; ++g) math_group(op, x, count, out, g, bs);
+    return HE_OK;
+}
+
+he_status he_host_episode_wrap(const uint32_t* t, const uint32_t* k, const uint32_t* T, int64_t count, int32_t le,
+                               uint32_t* out) {
+    if (count < 0 || ((!t || !k || !T || !out) && count > 0)) return HE_EINVAL;
+    for (int64_t j = 0; j < count; ++j)
+        out[j] = le ? episode_wrap_le(t[j], k[j], T[j]) : episode_wrap(t[j], k[j], T[j]);
     return HE_OK;
 }
 

@@ -356,6 +356,10 @@ he_status he_host_div_by(const double* a, int64_t count, double b, double* out);
 he_status he_host_box_muller(const double* u1, const double* u2, int64_t count, double* z1, double* z2);
 /* f32 twin for the obs quotients by per-handle constants (must equal IEEE a[k] / b). */
 he_status he_host_div_byf(const float* a, int64_t count, float b, float* out);
+/* The LDS kernels' episode-step wrap (he_math.h episode_wrap; le != 0: episode_wrap_le, which
+ * needs k[j] <= T[j]) on host arrays, for tests: out[j] = (t[j] + k[j]) % T[j], t[j] < T[j]. */
+he_status he_host_episode_wrap(const uint32_t* t, const uint32_t* k, const uint32_t* T, int64_t count, int32_t le,
+                               uint32_t* out);
 /* Device builds of the same RNG for tests (DEVICE pointers, stream-ordered): the 4 Philox
  * words of (seed, env_ids[k], step_index[k]) into words[4k..4k+3] (= rocRAND
  * rocrand_init(seed, env_ids[k], 4 step_index[k]) + rocrand4) and the Box-Muller pair the
