@@ -195,6 +195,19 @@ HE_HD float div_f32_byf(float a, float b, float y) {
     return (a == 0.0f || !(fabsf(a) <= 3.4028234663852886e38f)) ? q : res;
 }
 
+// div_f32_by / div_f32_byf for a dividend known to be finite and not zero (the tame blocks of the
+// LDS obs stepper: S in [64, 2^23], C and P normal f32 numbers): the select above takes `res`, so
+// it -- and div_f32_by's conversion of q -- is left out.  The same bits for such an a.
+HE_HD float div_f32_by_nz(float a, double b, double y64) {
+    const double ad = (double)a;
+    const double q = ad * y64;
+    return (float)fma(fma(-q, b, ad), y64, q);
+}
+HE_HD float div_f32_byf_nz(float a, float b, float y) {
+    const float q = a * y;
+    return fmaf(fmaf(-q, b, a), y, q);
+}
+
 // np.rint(f32).astype(int64) then np.clip(., -mt, mt)  (hedging_env_v2.py:184-188).
 // x86 cvttss2si maps NaN and |x| >= 2^63 to INT64_MIN, which the clip sends to -mt.
 // Branch-free (selects only): the step kernels keep whole steps in one basic block.

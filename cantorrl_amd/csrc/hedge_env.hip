@@ -152,6 +152,7 @@ struct Params {
     double g_sst;                // sigma*sqrt(T) (f64)
     double g_inv_sst;            // 1/(sigma*sqrt(T))
     float g_sst_f, g_inv_sst_f;  // f32 twins for greeks_fast
+    int32_t lds_tame;            // the LDS obs stepper may take its tame body (lds_tame_handle)
     float sqrt_tenor_f;
     double h_kappa, h_theta, h_xi, h_rho, h_sqrt1mrho2;
     int32_t den_const;      // generate: reward denominator of the shared S0 (all envs)
@@ -349,8 +350,10 @@ __device__ __forceinline__ float4 greeks(const Params& p, float S, float v) {
 // exp and branchy rational approximations.  Error of the f32 evaluation: relative
 // < 4.8e-7 where the tail is > 0.1, < 1.3e-6 below it, absolute < 2.2e-7 -- inside the
 // obs tolerance (OBS_RTOL 1e-6, OBS_ATOL 1e-7) against the reference's f64 ndtr.
+// TAME: |d1| < 14 (the caller's bound), so the cap is the identity and is left out.
+template <bool TAME = false>
 __device__ __forceinline__ float ncdf_tail(float d1, float ph) {
-    const float a = fminf(fabsf(d1), 14.0f);
+    const float a = TAME ? fabsf(d1) : fminf(fabsf(d1), 14.0f);
     const float w = 2.0f * __builtin_amdgcn_rcpf(a + 2.0f);
     float r = -2.690903097e-02f;
     r = fmaf(r, w, 6.361111253e-02f);
@@ -458,14 +461,20 @@ __device__ __forceinline__ float div_f32_core(float a, float b) {
 // logf for x >= FLT_MIN (or inf / NaN): ocml's logf -- v_log_f32, then the product with ln 2 in
 // two parts -- without the denormal scaling it skips there (the same operations, the same bits;
 // with expf_nonpos: headline 270.3 -> 267.4 us, 3 of 3 same-box pairs, r05s28_ab_log_exp.txt)
+// FINITE: x is a positive normal number, so v_log_f32's result is finite and the select takes hi + t.
+template <bool FINITE = false>
 __device__ __forceinline__ float logf_normal(float x) {
     const float r = __builtin_amdgcn_logf(x);
     const float hi = r * 0x1.62e42ep-1f;
     float t = fmaf(r, 0x1.62e42ep-1f, -hi);
     t = fmaf(r, 0x1.efa39ep-25f, t);
+    if constexpr (FINITE) return hi + t;
     return (fabsf(r) < __builtin_inff()) ? hi + t : r;
 }
 // expf for x <= 0 (or NaN): ocml's expf without its overflow select (never taken there)
+// INRANGE: -0x1.9d1da0p+6 <= x <= 0 (x = -d1^2 / 2 with |d1| < 14 is above -98), so the underflow
+// select takes v.
+template <bool INRANGE = false>
 __device__ __forceinline__ float expf_nonpos(float x) {
     const float hi = x * 0x1.715476p+0f;
     float t = fmaf(x, 0x1.715476p+0f, -hi);
@@ -473,10 +482,33 @@ __device__ __forceinline__ float expf_nonpos(float x) {
     t = fmaf(x, 0x1.4ae0bep-26f, t);
     const float e = __builtin_amdgcn_exp2f((hi - k) + t);
     const float v = ldexpf(e, (int)k);
+    if constexpr (INRANGE) return v;
     return (x >= -0x1.9d1da0p+6f || x != x) ? v : 0.0f;
 }
 
-__device__ __forceinline__ float4 greeks_lean(float S, float num_drift, float inv_sst_f, float sstf) {
+// TAME (the obs stepper's tame blocks: 64 <= S <= 2^23 in every lane, and the handle's
+// Params::lds_tame bounds): each guard below whose arm is then fixed is compiled out, its
+// precondition beside it -- the operations that remain and their operands are the same.
+template <bool TAME>
+__device__ __forceinline__ float4 greeks_lean_t(float S, float num_drift, float inv_sst_f, float sstf) {
+    const float K = rintf(S);   // >= 64: np_maxf(K, 1e-6f) is K, and K == 0 / K < 0 never hold
+    // S / K is within 2^-7 of 1 (|S - K| <= 1/2 <= K 2^-7): a normal number, its log finite and at
+    // most 0.00785 in magnitude.  lds_tame: (0.008 + |num_drift|) inv_sst_f < 14 with margin, so
+    // |d1| < 14 -- expf_nonpos's argument is in range and ncdf_tail's cap is the identity
+    const float num = logf_normal<true>(div_f32_core(S, K)) + num_drift;
+    const float d1 = num * inv_sst_f;
+    const float ph = expf_nonpos<true>(-0.5f * (d1 * d1)) * 0.398942280401432678f;
+    const float tail = ncdf_tail<true>(d1, ph);
+    const float cd = (d1 >= 0.0f) ? 1.0f - tail : tail;
+    const float pd = (d1 >= 0.0f) ? -tail : tail - 1.0f;
+    // lds_tame: 64 sstf >= 1e-9f, and S sstf >= 64 sstf (rounding is monotonic, 64 sstf exact), so
+    // gamma's |gd| < 1e-9 arm is never taken; S > 1e-6, so neither are the three `tiny` arms
+    const float gd = S * sstf;
+    const float gam = ph * __builtin_amdgcn_rcpf(gd);
+    return make_float4(cd, gam, pd, 0.0f);
+}
+template <>
+__device__ __forceinline__ float4 greeks_lean_t<false>(float S, float num_drift, float inv_sst_f, float sstf) {
     const float K = rintf(S);
     const float Kc = np_maxf(K, 1e-6f);
     const float num = logf_normal(div_f32_core(S, Kc)) + num_drift;   // f32 in the reference too
@@ -496,6 +528,9 @@ __device__ __forceinline__ float4 greeks_lean(float S, float num_drift, float in
     pd = tiny ? pt : pd;
     gam = tiny ? 0.0f : gam;
     return make_float4(cd, gam, pd, 0.0f);
+}
+__device__ __forceinline__ float4 greeks_lean(float S, float num_drift, float inv_sst_f, float sstf) {
+    return greeks_lean_t<false>(S, num_drift, inv_sst_f, sstf);
 }
 
 // np.clip(n, -maxh, maxh) of the steppers' positions (maxh >= 0, he_create): one v_med3_i32 (the
@@ -521,8 +556,16 @@ __device__ __forceinline__ float lag_return(float S, float Sp) {
 // dividend capped at Sp -- every (S - Sp) / Sp >= 1 clips to 1 and Sp / Sp = 1 exactly, so the
 // value is the same, and an infinite S (an f32 overflow of the f64 price) gives the reference's
 // clip(inf) = 1 instead of div_f32_core's inf - inf = NaN; a NaN stays NaN (the compare is false)
+// TAME (64 <= S, Sp <= 2^23): Sp != 0, and q is finite (|d| < 2^23, Sp >= 64), so the clip --
+// two compares and two selects that keep a NaN -- is one v_med3_f32, which gives the same value
+// for every finite q, -0 included.  The cap stays: it is what makes every d > Sp give exactly 1.
+template <bool TAME = false>
 __device__ __forceinline__ float lag_return_lean(float S, float Sp) {
     const float d = S - Sp;
+    if constexpr (TAME) {
+        const float q = div_f32_core((d > Sp) ? Sp : d, Sp);
+        return __builtin_amdgcn_fmed3f(q, -1.0f, 1.0f);
+    }
     float q = div_f32_core((d > Sp) ? Sp : d, Sp);
     HE_OPAQUE1(q);
     return (Sp == 0.0f) ? 0.0f : np_clipf(q, -1.0f, 1.0f);
@@ -2153,6 +2196,10 @@ struct LdsMarketT {
     // the book's options, copied at launch start (config 4: 10.38 -> 8.98 ms per launch against
     // reading them through the scalar cache)
     BookOpt bopt[BOOK ? HE_BOOK_MAX : 1];
+    // per market buffer and producer wave: all ones when every slot the wave made for the block is
+    // tame (lds_producer's test), 0 otherwise -- written before the block's barrier, read by the
+    // obs stepper after it.  Last, so no other member's offset moves.
+    uint32_t tame[NB][2];
 };
 static_assert(kLdsM > 8 || sizeof(LdsMarketT<HE_MODE_GBM, false>) <= 40 * 1024, "4 workgroups per CU");
 static_assert(kLdsM > 8 || sizeof(LdsMarketT<HE_MODE_GBM, false, true>) <= 40 * 1024 - 64, "4 workgroups per CU");
@@ -2221,7 +2268,7 @@ __device__ __forceinline__ void flush_obs_full(const float* img, float* out, int
 // tracks and the obs greeks it re-evaluates from the slot's market; no action crosses the waves,
 // and the LDS block pipeline is the stored-action rollout's.  The reward stepper keeps the
 // evaluation loops' episode sums and records (step_body's POL), the obs stepper stores the actions.
-template <int MODE, bool BOOK, bool LEAN, bool OBS, bool POL = false, bool PLAIN_OK = false>
+template <int MODE, bool BOOK, bool LEAN, bool OBS, bool POL = false, bool PLAIN_OK = false, bool TAME_OK = false>
 __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& io, int k_steps, const Market& cur,
                                             LdsMarketT<MODE, BOOK, LEAN>& L, int64_t base) {
     constexpr int D = kLdsPrefetch;
@@ -2391,7 +2438,16 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
     // Both steppers and the producers make the test from their own counters of the same episode
     // steps.  Envs reset apart (lanes at different episode steps) mostly take the general body.
     constexpr bool kPlain = PLAIN_OK && LEAN && !POL;
-    auto run_blk = [&](auto&& step) {
+    // TAME (the GBM obs stepper without a book, TAME_OK instances): a plain block whose market both
+    // producer waves flagged tame (L.tame: every S in [64, 2^23), C and P normal f32 numbers), on a
+    // handle with Params::lds_tame, and with this wave's lagged price of slot 0 -- carried from
+    // the block before or the reset, so not covered by the producers' flag -- in [64, 2^23] in
+    // every lane (pre_ok), runs a third instance of the slots with the corner-case guards such a
+    // market cannot meet compiled out (obs_step's TAME): every select's one possible arm, so the
+    // same bits.  The `plain` argument of a step is 0 (general), 1 (plain) or 2 (plain and tame).
+    constexpr bool kTame = kPlain && TAME_OK && OBS && MODE == HE_MODE_GBM && !BOOK;
+    const bool tame_h = kTame && p.lds_tame != 0;
+    auto run_blk = [&](auto&& step, auto&& pre_ok) {
         LDS_BAR();  // block 0 produced
         for (int b = 0; b < nfull; ++b) {
 #if defined(HE_LDS_DIAG) && HE_LDS_DIAG == 2
@@ -2412,8 +2468,17 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
                 }
             };
             if constexpr (kPlain) {
-                if (__ballot((int32_t)(e.t + (uint32_t)kLdsM) >= p.T) == 0ull) slots(std::true_type{});
-                else slots(std::false_type{});
+                if (__ballot((int32_t)(e.t + (uint32_t)kLdsM) >= p.T) == 0ull) {
+                    if constexpr (kTame) {
+                        const uint32_t tw = __builtin_amdgcn_readfirstlane(L.tame[buf][0] & L.tame[buf][1]);
+                        if (tame_h && tw != 0u && __ballot(!pre_ok()) == 0ull) slots(std::integral_constant<int, 2>{});
+                        else slots(std::true_type{});
+                    } else {
+                        slots(std::true_type{});
+                    }
+                } else {
+                    slots(std::false_type{});
+                }
             } else {
                 slots(std::false_type{});
             }
@@ -2447,6 +2512,8 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
             for (int c = 0; c < kObs; ++c) ro[c] = p.rstv[4 + c];
             float preS = pre.S;
             if (e.t != 0) preS = (float)cur.S[i];
+            const float dv12 = np_clipf(var_f - var_f, -1.0f, 1.0f);
+            auto pre_ok = [&] { return preS >= 64.0f && preS <= 8388608.0f; };
             // Heston: the slot's f32 variance v_t (obs column 5, the greeks' sigma) and the previous
             // step's (column 12's change)
             float preV = rst.v;
@@ -2462,6 +2529,8 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
             asm volatile("" : "+v"(row0), "+v"(row1));
             auto obs_step = [&](int buf, int sl, int k, float2 ak, auto full, auto plain) {
                 constexpr bool PLAIN = decltype(plain)::value;   // no episode ends in this block
+                // and the block is tame: r0.x and preS in [64, 2^23], r0.y and rP normal numbers
+                constexpr bool TAME = (int)decltype(plain)::value == 2;
                 const float2 r0 = L.sc[buf][sl][lane];
                 const float rP = L.pp[buf][sl][lane];
                 const float vk = HESTON ? L.vv[HESTON ? buf : 0][HESTON ? sl : 0][lane] : var_f;
@@ -2470,7 +2539,7 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
                 // slot's variance, the generic steppers' greeks_fast<false>
                 float4 g;
                 if constexpr (HESTON) g = greeks_fast<false>(p, r0.x, vk);
-                else g = greeks_lean(r0.x, gnd, gis, gsf);
+                else g = greeks_lean_t<TAME>(r0.x, gnd, gis, gsf);
                 if constexpr (POL) {   // the policy on the obs row this env stands at (step_body's POL)
                     ak = policy_action(p, pol, e.call, e.put, po3, po4, pcd, ppd);
                     if (io.pol.act_out) {
@@ -2494,13 +2563,19 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
                 // C and P through f64 (div_f32_by): a deep out-of-the-money mark of a rolling ATM
                 // option can be tiny -- |d| past ~13 at a small S or sigma, in GBM as in Heston --
                 // where the f32 step's residual leaves the normal range
-                if constexpr (HESTON) {
-                    o[0] = div_f32_by(r0.x, s0s_d, inv_s0s_d);   // Heston: the same, S included
+                if constexpr (TAME) {   // finite, non-zero dividends: the quotients without their select
+                    o[0] = div_f32_byf_nz(r0.x, s0s_f, inv_s0s_f);
+                    o[1] = div_f32_by_nz(r0.y, s0s_d, inv_s0s_d);
+                    o[2] = div_f32_by_nz(rP, s0s_d, inv_s0s_d);
                 } else {
-                    o[0] = div_f32_byf(r0.x, s0s_f, inv_s0s_f);
+                    if constexpr (HESTON) {
+                        o[0] = div_f32_by(r0.x, s0s_d, inv_s0s_d);   // Heston: the same, S included
+                    } else {
+                        o[0] = div_f32_byf(r0.x, s0s_f, inv_s0s_f);
+                    }
+                    o[1] = div_f32_by(r0.y, s0s_d, inv_s0s_d);
+                    o[2] = div_f32_by(rP, s0s_d, inv_s0s_d);
                 }
-                o[1] = div_f32_by(r0.y, s0s_d, inv_s0s_d);
-                o[2] = div_f32_by(rP, s0s_d, inv_s0s_d);
                 o[3] = div_int_byf((float)cc, maxh_f, inv_maxh_f);
                 o[4] = div_int_byf((float)qq, maxh_f, inv_maxh_f);
                 o[5] = vk;
@@ -2509,8 +2584,13 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
                 o[8] = g.y;
                 o[9] = g.z;
                 o[10] = g.y;
-                o[11] = lag_return_lean(r0.x, preS);
-                o[12] = (preS == 0.0f) ? 0.0f : np_clipf(vk - (HESTON ? preV : var_f), -1.0f, 1.0f);
+                o[11] = lag_return_lean<TAME>(r0.x, preS);
+                // GBM: the variance never changes, so the column is (preS == 0) ? 0 : dv12 with dv12 =
+                // clip(var_f - var_f) made once per launch -- +0 for a finite variance, NaN otherwise;
+                // in a tame block the literal (preS >= 64, and lds_tame has the variance finite)
+                if constexpr (HESTON) o[12] = (preS == 0.0f) ? 0.0f : np_clipf(vk - preV, -1.0f, 1.0f);
+                else if constexpr (TAME) o[12] = 0.0f;
+                else o[12] = (preS == 0.0f) ? 0.0f : dv12;
                 // staged in LDS (two tiles, alternating by step: the next step's row writes
                 // do not wait behind this step's read-back) and stored as whole 16-B lines
                 float* const tile = L.stage[k & 1];
@@ -2548,11 +2628,11 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
             if (wrows == kLdsEnvs)
                 run_blk([&](int buf, int sl, int k, float2 ak, auto, auto plain) {
                     obs_step(buf, sl, k, ak, std::true_type{}, plain);
-                });
+                }, pre_ok);
             else
                 run_blk([&](int buf, int sl, int k, float2 ak, auto, auto plain) {
                     obs_step(buf, sl, k, ak, std::false_type{}, plain);
-                });
+                }, pre_ok);
         } else {
             const double tcpc = p.tcpc, slip_frac = p.slip_frac, lam = p.lam, w = p.w, theta = p.theta;
             const double shares_d = p.shares_d, inv_shares = p.inv_shares, den = p.den, inv_den = p.inv_den;
@@ -2652,7 +2732,7 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
                 e.cash = term ? init_cash : cash;
                 preC100 = term ? rstC100 : C100;
                 preP100 = term ? rstP100 : P100;
-            });
+            }, [] { return false; });
         }
     } else {
         // (the generic steps' Params fields pinned in SGPRs instead of the scalar-cache reloads:
@@ -2727,9 +2807,11 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
             }
         };
         if (OBS && wrows == kLdsEnvs)
-            run_blk([&](int buf, int sl, int k, float2 ak, auto, auto) { step(buf, sl, k, ak, std::true_type{}); });
+            run_blk([&](int buf, int sl, int k, float2 ak, auto, auto) { step(buf, sl, k, ak, std::true_type{}); },
+                    [] { return false; });
         else
-            run_blk([&](int buf, int sl, int k, float2 ak, auto, auto) { step(buf, sl, k, ak, std::false_type{}); });
+            run_blk([&](int buf, int sl, int k, float2 ak, auto, auto) { step(buf, sl, k, ak, std::false_type{}); },
+                    [] { return false; });
     }
     LDS_T1(OBS ? 1 : 0);
     if (!OBS && i0 < N) {
@@ -2766,7 +2848,7 @@ __device__ __forceinline__ void prod_prio_toggle(bool up) {
 // Producer waves: block bp of 64 envs into LDS buffer bp & 1 while the steppers consume
 // block bp - 1.  pw = producer wave index (kLdsPEnvs envs each).  Lanes past the last
 // env mirror env N-1 like the steppers' (identical values, identical addresses).
-template <int MODE, bool BOOK, bool LEAN, bool PLAIN_OK = false>
+template <int MODE, bool BOOK, bool LEAN, bool PLAIN_OK = false, bool TAME_OK = false>
 __device__ __forceinline__ void lds_producer(const Params& p, int k_steps, const Market& cur,
                                              LdsMarketT<MODE, BOOK, LEAN>& W, int64_t base, int pw) {
     using G = LdsGeom<MODE, BOOK>;
@@ -2800,6 +2882,9 @@ __device__ __forceinline__ void lds_producer(const Params& p, int k_steps, const
     double Vbs = HESTON ? cur.v[pi] : 0.0;           // Heston: f64 variance before it
     double Mbs = BOOK ? cur.M[pi] : 0.0;             // book: running max of S before it
     const int sl0 = sub * kLdsH;
+    // TAME_OK instances (the lean GBM producers of the stored-action rollout): every block's tame
+    // flag for the obs stepper (LdsMarketT::tame), and the price chain's own slots by half-wave
+    constexpr bool kTame = TAME_OK && PLAIN_OK && LEAN && !HESTON && !BOOK && kLdsLanes == 2;
     LDS_T0();
     for (int bp = 0; bp <= nb; ++bp) {
 #if defined(HE_LDS_DIAG) && HE_LDS_DIAG == 1
@@ -2966,7 +3051,27 @@ __device__ __forceinline__ void lds_producer(const Params& p, int k_steps, const
 #pragma unroll
             for (int h = 0; h < kLdsH; ++h) Mx[h] = Mbs;
             double S = Sbs, Sin = Sbs, Mr = Mbs;
-            {
+            if constexpr (kTame && FULL) {
+                // the same products in the same order with the same clamp, all kLdsM values kept: the
+                // lane's own slots are the chain's first or second half by half-wave -- kLdsH selects
+                // on one compare, where the j == sl0 + h tests below (sl0 is not a compile-time
+                // value) are kLdsM * kLdsH selects
+                static_assert(!kTame || kLdsM == 2 * kLdsH, "two lanes per env");
+                double Sa[kLdsM];
+                uint32_t tp = tpb;
+#pragma unroll
+                for (int j = 0; j < kLdsM; ++j) {
+                    if (!PLAIN && tp == 0) S = p.s0;   // autoreset: a new episode starts from S0
+                    const double Sn = S * eall[j];
+                    S = (Sn < 1e-8) ? 1e-8 : Sn;  // np.maximum(., 1e-8), NaN kept
+                    if (!PLAIN) tp = (tp + 1 == T) ? 0u : tp + 1;
+                    Sa[j] = S;
+                }
+                const bool hi = sub != 0;
+#pragma unroll
+                for (int h = 0; h < kLdsH; ++h) Sx[h] = hi ? Sa[kLdsH + h] : Sa[h];
+                Sin = hi ? Sa[kLdsH - 1] : Sbs;
+            } else {
                 uint32_t tp = tpb;
 #pragma unroll
                 for (int j = 0; j < kLdsM; ++j) {
@@ -3012,6 +3117,35 @@ __device__ __forceinline__ void lds_producer(const Params& p, int k_steps, const
                     Km[h] = rint(Sm[h]);   // marks<GBM>: the rolling-ATM strike K = round(S)
                 }
                 bs_call_put_n<kLdsH>(Sm, Km, p.bs, lkC, lkP);
+            }
+            if constexpr (kTame) {
+                // the block's tame flag, before its barrier.  A plain lockstep block: every S of the
+                // lane's slots in [64, 2^23) and every C and P in [2^-126, 2^127), so their f32
+                // values in LDS are in [64, 2^23] and normal numbers ((float) is monotonic).  Tested
+                // on the high words of the f64 values as unsigned integers -- for positive numbers
+                // their order is the numbers' own, and a negative number, an infinity or a NaN has
+                // a high word above every bound here -- by 32-bit min / max chains.  Every other
+                // body (a boundary block, a ragged one) says 0.
+                uint32_t verdict = 0u;
+                if constexpr (LOCK && PLAIN) {
+                    uint32_t smin = (uint32_t)__double2hiint(Sx[0]), smax = smin;
+                    uint32_t mmin = (uint32_t)__double2hiint(lkC[0]), mmax = mmin;
+#pragma unroll
+                    for (int h = 0; h < kLdsH; ++h) {
+                        const uint32_t sh = (uint32_t)__double2hiint(Sx[h]);
+                        const uint32_t ch = (uint32_t)__double2hiint(lkC[h]), ph = (uint32_t)__double2hiint(lkP[h]);
+                        smin = sh < smin ? sh : smin;
+                        smax = sh > smax ? sh : smax;
+                        mmin = ch < mmin ? ch : mmin;
+                        mmax = ch > mmax ? ch : mmax;
+                        mmin = ph < mmin ? ph : mmin;
+                        mmax = ph > mmax ? ph : mmax;
+                    }
+                    // high words of 64.0, 2^23, 2^-126 and 2^127
+                    const bool ok = smin >= 0x40500000u && smax < 0x41600000u && mmin >= 0x38100000u && mmax < 0x47e00000u;
+                    verdict = __ballot(!ok) == 0ull ? 0xffffffffu : 0u;
+                }
+                W.tame[wb][pw] = verdict;
             }
             if constexpr (LOCK) {
 #pragma unroll
@@ -3219,9 +3353,10 @@ __global__ __launch_bounds__((LdsGeom<MODE, BOOK>::threads), (LdsGeom<MODE, BOOK
     }
     if constexpr (!PERSIST) {   // one workgroup per 64-env tile
         const int64_t base = (int64_t)blockIdx.x * kLdsEnvs;
+        // the tame blocks: the stored-action instance only (the policy and persistent ones as they were)
         if (wave == 0) lds_stepper<MODE, BOOK, LEAN, false, POL, true>(p, s, io, k_steps, cur, lm, base);
-        else if (wave == 1) lds_stepper<MODE, BOOK, LEAN, true, POL, true>(p, s, io, k_steps, cur, lm, base);
-        else lds_producer<MODE, BOOK, LEAN, true>(p, k_steps, cur, lm, base, wave - 2);
+        else if (wave == 1) lds_stepper<MODE, BOOK, LEAN, true, POL, true, !POL>(p, s, io, k_steps, cur, lm, base);
+        else lds_producer<MODE, BOOK, LEAN, true, !POL>(p, k_steps, cur, lm, base, wave - 2);
         return;
     }
     // PERSIST (launch_lds_rollout, more tiles than the device holds workgroups at once): a
@@ -4114,6 +4249,19 @@ static bool is_generate(const he_env* env) { return env->cfg.mode != HE_MODE_REP
 static uint64_t* g_tim = nullptr;
 #endif
 
+// The two per-handle facts behind the LDS obs stepper's tame body (greeks_lean_t<true>, for
+// prices S >= 64), from the constant-variance greeks' f32 constants:
+//  - |d1| < 14: |log(S / rint S)| <= |log(1 - 2^-7)| < 0.00785 there; taken as 0.008 -- 2 % over,
+//    against relative rounding errors of the f32 log, sum and product near 1e-7 each -- and a
+//    further 1e-5 on the product;
+//  - S sigma sqrt(T) >= 1e-9 as f32 (gamma's guard): 64 sst_f is exact.
+// And a finite f32 variance (obs column 12 is then +0).  A NaN constant fails the compares.
+static bool lds_tame_handle(const Params& p) {
+    const double d1_max = (0.008 + fabs((double)p.g_num_drift)) * fabs((double)p.g_inv_sst_f) * (1.0 + 1e-5);
+    return d1_max < 14.0 && p.g_inv_sst_f > 0.0f && 64.0f * p.g_sst_f >= 1e-9f && 64.0f * p.g_sst_f < 3.0e38f &&
+           fabsf(p.var_f) <= 3.4028234663852886e38f;
+}
+
 static void fill_params(he_env* env) {
     const he_config& c = env->cfg;
     Params& p = env->p;
@@ -4181,6 +4329,7 @@ static void fill_params(he_env* env) {
     p.g_inv_sst = 1.0 / p.g_sst;
     p.g_sst_f = (float)p.g_sst;
     p.g_inv_sst_f = (float)p.g_inv_sst;
+    p.lds_tame = lds_tame_handle(p) ? 1 : 0;
     p.sqrt_tenor_f = (float)p.sqrt_tenor;
     p.h_kappa = c.heston_kappa;
     p.h_theta = c.heston_theta;
