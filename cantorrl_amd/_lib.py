@@ -123,6 +123,7 @@ EXPORTS = [
     "he_vecnorm_apply", "he_vecnorm_attach", "he_vecnorm_attach_eval", "he_vecnorm_reset", "he_fixed_european_marks", "he_bs_delta_hedge", "he_count_nonfinite",
     "he_device_rng", "he_device_math", "he_host_math", "he_episode_summaries", "he_host_alloc", "he_host_free",
     "he_stream_wait", "he_step_signal", "he_signal_seq", "he_signal_wait", "he_host_episode_wrap",
+    "he_host_vecnorm_sb3",
 ]
 
 
@@ -136,8 +137,14 @@ class HeVecnormParams(ctypes.Structure):
         ("clip_obs", ctypes.c_double),
         ("clip_reward", ctypes.c_double),
         ("epsilon", ctypes.c_double),
-        ("reserved", ctypes.c_int32 * 4),
+        ("moments", ctypes.c_int32),   # HE_VN_MOMENTS_F64 (0) / HE_VN_MOMENTS_SB3
+        ("reserved", ctypes.c_int32 * 3),
     ]
+
+
+HE_VN_MOMENTS_F64, HE_VN_MOMENTS_SB3 = range(2)
+HE_VN_SB3_MAX_ENVS = 4096
+VN_MOMENTS = {"f64": HE_VN_MOMENTS_F64, "sb3": HE_VN_MOMENTS_SB3}
 
 
 class HeVecnormOut(ctypes.Structure):
@@ -204,6 +211,7 @@ def load(path=LIB_PATH):
         "he_vecnorm_attach": (i32, [vp, ctypes.POINTER(HeVecnormParams), vp, vp, vp]),
         "he_vecnorm_attach_eval": (i32, [vp, ctypes.POINTER(HeVecnormParams), ctypes.POINTER(HeVecnormOut)]),
         "he_vecnorm_reset": (i32, [ctypes.POINTER(HeVecnormParams), i64] + [vp] * 5 + [vp]),
+        "he_host_vecnorm_sb3": (i32, [ctypes.POINTER(HeVecnormParams), i64] + [vp] * 9),
         "he_fixed_european_marks": (i32, [vp, i64, i32, ctypes.c_double, vp, vp, vp, vp]),
         "he_bs_delta_hedge": (i32, [vp, i64, i32, ctypes.c_double, ctypes.c_double, vp, vp]),
         "he_count_nonfinite": (i32, [vp, i64, vp, vp]),

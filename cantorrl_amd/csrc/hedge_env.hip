@@ -5503,6 +5503,11 @@ he_status he_vecnorm_attach(he_env* env, const he_vecnorm_params* p, double* ret
         return HE_OK;
     }
     if (p->obs_dim != kObs || !isfinite(p->gamma)) return fail(env, HE_EINVAL, "bad he_vecnorm_params");
+    if (p->moments != HE_VN_MOMENTS_F64)
+        return fail(env, HE_EINVAL, p->moments == HE_VN_MOMENTS_SB3
+                                        ? "he_vecnorm_attach takes moments = HE_VN_MOMENTS_F64: the row-order sums of "
+                                          "HE_VN_MOMENTS_SB3 do not split into per-workgroup partials (use he_vecnorm_step)"
+                                        : "bad he_vecnorm_params (moments)");
     if (!returns || !stats || !scratch) return fail(env, HE_EINVAL, "returns / stats / scratch are NULL");
     if (kEpb != vn::kVnChunk)  // he_vecnorm_apply merges one partial per 256 rows
         return fail(env, HE_EINVAL, "he_vecnorm_attach needs 256 envs per step workgroup (HE_STEP_EPW=64)");
@@ -5532,6 +5537,10 @@ he_status he_vecnorm_attach_eval(he_env* env, const he_vecnorm_params* p, const 
     }
     if (p->obs_dim != kObs || p->training || !(p->clip_obs >= 0.0) || !(p->clip_reward >= 0.0) || !(p->epsilon >= 0.0))
         return fail(env, HE_EINVAL, "bad he_vecnorm_params (the eval arm takes training = 0)");
+    if (p->moments != HE_VN_MOMENTS_F64 && p->moments != HE_VN_MOMENTS_SB3)
+        return fail(env, HE_EINVAL, "bad he_vecnorm_params (moments)");
+    if (p->moments == HE_VN_MOMENTS_SB3 && env->cfg.n_envs > HE_VN_SB3_MAX_ENVS)
+        return fail(env, HE_EINVAL, "HE_VN_MOMENTS_SB3 covers up to %d envs", HE_VN_SB3_MAX_ENVS);
     if (!out || !out->stats || !out->returns || !out->obs_out || !out->reward_out)
         return fail(env, HE_EINVAL, "he_vecnorm_out: stats / returns / obs_out / reward_out are NULL");
     if ((out->ep_return != nullptr) != (out->ep_length != nullptr) ||
@@ -5542,6 +5551,7 @@ he_status he_vecnorm_attach_eval(he_env* env, const he_vecnorm_params* p, const 
     vn::ApplyArgs a = {};
     a.norm_obs = p->norm_obs != 0;
     a.norm_reward = p->norm_reward != 0;
+    a.sb3 = p->moments == HE_VN_MOMENTS_SB3;
     a.clip_obs = p->clip_obs;
     a.clip_rew = p->clip_reward;
     a.eps = p->epsilon;

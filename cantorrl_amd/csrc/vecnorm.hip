@@ -19,14 +19,21 @@
 // Deterministic for a given grid; no atomics and no waiting between workgroups (the
 // kernel boundary publishes the partials).  Eval mode (no statistics update) is the
 // second launch alone.  68 B of obs + reward read and written per env.
+//
+// moments = HE_VN_MOMENTS_SB3 (n <= 4096) is one launch of one workgroup instead,
+// vn_sb3_kernel: SB3's own NumPy arithmetic bit for bit (vn_sb3.h) -- the f32 row-order sums
+// of the obs columns are one dependent chain per column, which no second workgroup could help.
 
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/hedge_env.h"
 #include "vn_moments.h"
+#include "vn_sb3.h"
 
 namespace {
 
@@ -60,6 +67,7 @@ struct VnArgs {
     int32_t* ep_len_done;
     const double* ep_reward;   // the env's f64 step rewards Monitor sums (he_info::reward_step)
     int reset;   // he_vecnorm_reset: returns = 0 instead of the discounted update
+    int sb3;     // moments = HE_VN_MOMENTS_SB3: vn_sb3_kernel
 };
 
 // RunningMeanStd.update_from_moments (SB3 common/running_mean_std.py), f64
@@ -294,6 +302,175 @@ __global__ void __launch_bounds__(kVnThreads) vn_apply_kernel(VnArgs a) {
     }
 }
 
+// moments = HE_VN_MOMENTS_SB3: the whole step -- batch moments, statistics update, apply -- in
+// one launch of ONE workgroup, n <= sb3::kMaxN rows, with the arithmetic of vn_sb3.h.
+//   returns   every thread updates its rows' returns into LDS; NumPy's pairwise sum takes one
+//             thread per tree node (sb3::pw_node): the leaves (<= 128 elements, eight
+//             accumulators) side by side, then the splits level by level, once for the mean
+//             and once over (x - mean)^2;
+//   obs       lanes 0 .. 12 carry the 13 f32 column chains in row order over 256-row chunks
+//             staged flat and coalesced into LDS (the next chunk's loads are in flight during
+//             the chain), one pass for the sums and one for the squares (a batch of <= 256
+//             rows stays in LDS for both);
+//   apply     lanes 0 .. 13 update and store the 14 statistics, then all threads normalize:
+//             the obs as a flat coalesced pass, then a row per thread as vn_apply_kernel.
+// The 2 n dependent f32 adds per column are the critical path at large n.
+__global__ void __launch_bounds__(kVnThreads) vn_sb3_kernel(VnArgs a) {
+    __shared__ float tile[kVnChunk * kD];
+    __shared__ double rbuf[sb3::kMaxN];
+    __shared__ double nval[sb3::kNodes];   // the pairwise tree's node sums, heap order
+    __shared__ double smean[kD], ssd[kD], srsd;
+    const int t = threadIdx.x;
+    const int n = (int)a.n;
+    const bool upd_ret = a.training && !a.reset;
+    double bret[2] = {0.0, 1.0};   // the returns' batch mean and variance (every thread)
+    // every load that depends on nothing first, in flight together: the first obs chunk, the
+    // thread's first row (reward, done flag, Monitor sums, running return) and the statistics
+    float nx[kD];
+    auto fetch = [&](int ch) {
+        const float* src = a.obs + (size_t)ch * kVnChunk * kD;
+        const int nf = (n - ch * kVnChunk < kVnChunk ? n - ch * kVnChunk : kVnChunk) * kD;
+#pragma unroll
+        for (int q = 0; q < kD; ++q) {
+            const int k = t + q * kVnThreads;
+            nx[q] = k < nf ? src[k] : 0.0f;
+        }
+    };
+    const bool tile_all = n <= kVnChunk;   // the whole batch is the first chunk: nx serves the apply too
+    if (a.upd_obs || tile_all) fetch(0);
+    RowIn pin = {};
+    if (!a.reset && t < n) pin = row_in(a, t);
+    double ret0 = upd_ret && t < n ? a.returns[t] : 0.0;
+    double st_mean = 0.0, st_var = 1.0, st_count = 0.0;   // lanes 0 .. 12 an obs column, lane 13 the returns
+    if (t < kD) {
+        st_mean = a.stats[t];
+        st_var = a.stats[kD + t];
+        st_count = a.stats[2 * kD];
+    } else if (t == kD) {
+        st_mean = a.stats[2 * kD + 1];
+        st_var = a.stats[2 * kD + 2];
+        st_count = a.stats[2 * kD + 3];
+    }
+    if (upd_ret) {
+        for (int r = t; r < n; r += kVnThreads) {
+            const double ret = r == t ? sb3::ret_update(ret0, a.gamma, pin.rw)
+                                      : sb3::ret_update(a.returns[r], a.gamma, a.reward[r]);
+            a.returns[r] = ret;
+            rbuf[r] = ret;
+        }
+        // thread t is node t of the pairwise tree: a leaf, a split or (most) nothing
+        const int levels = sb3::pw_levels(n);
+        const sb3::Node nd = t >= 1 && t < (2 << levels) ? sb3::pw_node(n, t) : sb3::Node{0, 0};
+        __syncthreads();
+        for (int pass = 0; pass < 2; ++pass) {
+            if (nd.n > 0 && nd.n <= sb3::kLeafMax) nval[t] = sb3::pw_leaf(rbuf + nd.lo, nd.n);
+            __syncthreads();
+            for (int d = levels - 1; d >= 0; --d) {   // the splits of level d, their halves done
+                if (nd.n > sb3::kLeafMax && (t >> d) == 1) nval[t] = nval[2 * t] + nval[2 * t + 1];
+                __syncthreads();
+            }
+            bret[pass] = nval[1] / (double)n;
+            if (pass == 0) {
+                for (int r = t; r < n; r += kVnThreads) {
+                    const double d = rbuf[r] - bret[0];
+                    rbuf[r] = d * d;
+                }
+                __syncthreads();   // also: every thread has read nval[1] before the second pass writes it
+            }
+        }
+    }
+    float bmean = 0.0f, bvar = 0.0f;   // lanes 0 .. 12: np.mean / np.var of their obs column
+    if (a.upd_obs) {
+        const int nchunks = (n + kVnChunk - 1) / kVnChunk;
+        const int iters = nchunks == 1 ? 1 : 2 * nchunks;   // one chunk serves both passes from LDS
+        float s = 0.0f, v = 0.0f;
+        for (int it = 0; it < iters; ++it) {
+#pragma unroll
+            for (int q = 0; q < kD; ++q) tile[t + q * kVnThreads] = nx[q];
+            __syncthreads();
+            const int ch = it < nchunks ? it : it - nchunks;
+            if (it + 1 < iters) fetch(it + 1 < nchunks ? it + 1 : it + 1 - nchunks);
+            const int rows = n - ch * kVnChunk < kVnChunk ? n - ch * kVnChunk : kVnChunk;
+            if (t < kD) {
+                if (it < nchunks) {
+                    s = sb3::col_sum(s, ch == 0, tile + t, rows);
+                    if (ch == nchunks - 1) bmean = s / (float)n;
+                }
+                if (it >= nchunks || nchunks == 1) v = sb3::col_sq(v, ch == 0, bmean, tile + t, rows);
+            }
+            __syncthreads();
+        }
+        bvar = v / (float)n;
+    }
+    // the 14 statistics: RunningMeanStd.update_from_moments, stored, and the columns' constants
+    if (t < kD) {
+        if (a.upd_obs) {
+            sb3::rms_update(&st_mean, &st_var, &st_count, (double)bmean, sb3::batch_m2_obs(bvar, n), (double)n);
+            a.stats[t] = st_mean;
+            a.stats[kD + t] = st_var;
+            if (t == 0) a.stats[2 * kD] = st_count;
+        }
+        smean[t] = st_mean;
+        ssd[t] = sb3::norm_sd(st_var, a.eps);
+    } else if (t == kD) {
+        if (upd_ret) {
+            sb3::rms_update(&st_mean, &st_var, &st_count, bret[0], bret[1] * (double)n, (double)n);
+            a.stats[2 * kD + 1] = st_mean;
+            a.stats[2 * kD + 2] = st_var;
+            a.stats[2 * kD + 3] = st_count;
+        }
+        srsd = sb3::norm_sd(st_var, a.eps);
+    }
+    __syncthreads();
+    // the obs element-wise, flat and coalesced: element k is column k % 13, stepped by
+    // 256 % 13 = 9 per trip without a division
+    {
+        const int nf = n * kD;
+        int c = t % kD;
+        if (tile_all) {   // the thread's elements are still in its registers
+#pragma unroll
+            for (int q = 0; q < kD; ++q) {
+                const int k = t + q * kVnThreads;
+                if (k < nf) a.obs_out[k] = a.norm_obs ? sb3::norm_obs(nx[q], smean[c], ssd[c], a.clip_obs) : nx[q];
+                c += kVnThreads % kD;
+                c = c >= kD ? c - kD : c;
+            }
+        } else {
+            for (int k = t; k < nf; k += kVnThreads) {
+                const float x = a.obs[k];
+                a.obs_out[k] = a.norm_obs ? sb3::norm_obs(x, smean[c], ssd[c], a.clip_obs) : x;
+                c += kVnThreads % kD;
+                c = c >= kD ? c - kD : c;
+            }
+        }
+    }
+    for (int r = t; r < n; r += kVnThreads) {
+        if (a.reset) {
+            a.returns[r] = 0.0;
+            continue;
+        }
+        const RowIn in = r == t ? pin : row_in(a, r);
+        a.rew_out[r] = a.norm_reward ? sb3::norm_rew(in.rw, srsd, a.clip_rew) : in.rw;
+        if (in.dn && a.tobs && a.tobs_out) {   // rare: per-row accesses
+            for (int c = 0; c < kD; ++c) {
+                const float x = a.tobs[(size_t)r * kD + c];
+                a.tobs_out[(size_t)r * kD + c] = a.norm_obs ? sb3::norm_obs(x, smean[c], ssd[c], a.clip_obs) : x;
+            }
+        }
+        if (in.dn) a.returns[r] = 0.0;   // self.returns[dones] = 0
+        if (a.ep_ret) {                    // Monitor: sum(rewards) of the f64 rewards, len(rewards)
+            const double er = in.er + in.rw64;
+            const int32_t el = in.el + 1;
+            if (in.dn) {
+                a.ep_ret_done[r] = er;
+                a.ep_len_done[r] = el;
+            }
+            a.ep_ret[r] = in.dn ? 0.0 : er;
+            a.ep_len[r] = in.dn ? 0 : el;
+        }
+    }
+}
+
 int blocks_for(int64_t n) {
     int64_t b = (n + kVnChunk - 1) / kVnChunk;   // one row per thread up to 65,536 envs
     if (b > kVnMaxBlocks) b = kVnMaxBlocks;
@@ -315,6 +492,12 @@ __global__ void init_kernel(double* stats) {
 }
 
 he_status launch(VnArgs& a, void* scratch, hipStream_t s, bool moments = true) {
+    if (a.sb3) {   // the whole step in one workgroup (the caller checked n <= sb3::kMaxN)
+        a.blocks = 1;
+        a.rows_per_block = (int)a.n;
+        hipLaunchKernelGGL(vn_sb3_kernel, dim3(1), dim3(kVnThreads), 0, s, a);
+        return hipGetLastError() == hipSuccess ? HE_OK : HE_EHIP;
+    }
     a.blocks = blocks_for(a.n);
     a.rows_per_block = (int)((a.n + a.blocks - 1) / a.blocks);
     a.part = (double*)scratch;   // [kVnMaxBlocks][kPart] partials, then the old statistics
@@ -328,7 +511,11 @@ he_status launch(VnArgs& a, void* scratch, hipStream_t s, bool moments = true) {
 
 bool params_ok(const he_vecnorm_params* p) {
     return p && p->obs_dim == kD && isfinite(p->gamma) && p->clip_obs >= 0.0 && p->clip_reward >= 0.0 &&
-           p->epsilon >= 0.0;
+           p->epsilon >= 0.0 && (p->moments == HE_VN_MOMENTS_F64 || p->moments == HE_VN_MOMENTS_SB3);
+}
+// moments = HE_VN_MOMENTS_SB3 covers one workgroup's rows
+bool count_ok(const he_vecnorm_params* p, int64_t n) {
+    return p->moments != HE_VN_MOMENTS_SB3 || n <= sb3::kMaxN;
 }
 
 VnArgs base_args(const he_vecnorm_params* p, int64_t n) {
@@ -342,6 +529,7 @@ VnArgs base_args(const he_vecnorm_params* p, int64_t n) {
     a.clip_obs = p->clip_obs;
     a.clip_rew = p->clip_reward;
     a.eps = p->epsilon;
+    a.sb3 = p->moments == HE_VN_MOMENTS_SB3;
     return a;
 }
 
@@ -388,7 +576,7 @@ static he_status vecnorm_step(const he_vecnorm_params* p, int64_t n, const float
                               void* scratch, float* obs_out, float* reward_out, float* terminal_obs_out,
                               double* ep_return, int32_t* ep_length, double* ep_return_done,
                               int32_t* ep_length_done, const double* ep_reward, void* stream, bool moments) {
-    if (!params_ok(p) || n < 0) return HE_EINVAL;
+    if (!params_ok(p) || n < 0 || !count_ok(p, n)) return HE_EINVAL;
     if (n == 0) return HE_OK;
     if (!obs || !reward || !returns || !stats || !scratch || !obs_out || !reward_out) return HE_EINVAL;
     if ((ep_return != nullptr) != (ep_length != nullptr) ||
@@ -428,13 +616,15 @@ he_status he_vecnorm_apply(const he_vecnorm_params* p, int64_t n, const float* o
                            const double* ep_reward, void* stream) {
     // training merges the fused partials, which cover <= 65,536 rows; frozen statistics read none
     if (p && p->training && n > (int64_t)kVnMaxBlocks * kVnThreads) return HE_EINVAL;
+    // he_vecnorm_attach makes no partials in this mode: nothing to merge
+    if (p && p->training && p->moments == HE_VN_MOMENTS_SB3) return HE_EINVAL;
     return vecnorm_step(p, n, obs, reward, done, terminal_obs, returns, stats, scratch, obs_out, reward_out,
                         terminal_obs_out, ep_return, ep_length, ep_return_done, ep_length_done, ep_reward, stream, false);
 }
 
 he_status he_vecnorm_reset(const he_vecnorm_params* p, int64_t n, const float* obs, double* returns, double* stats,
                            void* scratch, float* obs_out, void* stream) {
-    if (!params_ok(p) || n < 0) return HE_EINVAL;
+    if (!params_ok(p) || n < 0 || !count_ok(p, n)) return HE_EINVAL;
     if (n == 0) return HE_OK;
     if (!obs || !returns || !stats || !scratch || !obs_out) return HE_EINVAL;
     VnArgs a = base_args(p, n);
@@ -444,6 +634,70 @@ he_status he_vecnorm_reset(const he_vecnorm_params* p, int64_t n, const float* o
     a.stats = stats;
     a.obs_out = obs_out;
     return launch(a, scratch, (hipStream_t)stream);
+}
+
+he_status he_host_vecnorm_sb3(const he_vecnorm_params* p, int64_t n64, const float* obs, const float* reward,
+                              const uint8_t* done, const float* terminal_obs, double* returns, double* stats,
+                              float* obs_out, float* reward_out, float* terminal_obs_out) {
+    if (!params_ok(p) || n64 < 0 || n64 > sb3::kMaxN) return HE_EINVAL;
+    if (n64 == 0) return HE_OK;
+    const bool reset = reward == nullptr;
+    if (!obs || !returns || !stats || !obs_out || (!reset && !reward_out)) return HE_EINVAL;
+    const int n = (int)n64;
+    const bool training = p->training != 0, norm_obs = p->norm_obs != 0;
+    if (training && norm_obs) {   // obs_rms.update(obs): one f32 chain per column, row order
+        const double count0 = stats[2 * kD];
+        for (int c = 0; c < kD; ++c) {
+            const float bmean = sb3::col_sum(0.0f, true, obs + c, n) / (float)n;
+            const float bvar = sb3::col_sq(0.0f, true, bmean, obs + c, n) / (float)n;
+            double count = count0;
+            sb3::rms_update(&stats[c], &stats[kD + c], &count, (double)bmean, sb3::batch_m2_obs(bvar, n), (double)n);
+            stats[2 * kD] = count;
+        }
+    }
+    if (training && !reset) {     // returns = returns * gamma + reward; ret_rms.update(returns)
+        std::vector<double> buf(n);
+        double nval[sb3::kNodes], bret[2];
+        for (int r = 0; r < n; ++r) buf[r] = returns[r] = sb3::ret_update(returns[r], p->gamma, reward[r]);
+        const int levels = sb3::pw_levels(n);
+        for (int pass = 0; pass < 2; ++pass) {
+            for (int id = 1; id < (2 << levels); ++id) {
+                const sb3::Node nd = sb3::pw_node(n, id);
+                if (nd.n > 0 && nd.n <= sb3::kLeafMax) nval[id] = sb3::pw_leaf(buf.data() + nd.lo, nd.n);
+            }
+            for (int d = levels - 1; d >= 0; --d)
+                for (int id = 1 << d; id < (2 << d); ++id)
+                    if (sb3::pw_node(n, id).n > sb3::kLeafMax) nval[id] = nval[2 * id] + nval[2 * id + 1];
+            bret[pass] = nval[1] / (double)n;
+            if (pass == 0)
+                for (int r = 0; r < n; ++r) {
+                    const double d = buf[r] - bret[0];
+                    buf[r] = d * d;
+                }
+        }
+        sb3::rms_update(&stats[2 * kD + 1], &stats[2 * kD + 2], &stats[2 * kD + 3], bret[0], bret[1] * (double)n,
+                        (double)n);
+    }
+    double sd[kD];
+    for (int c = 0; c < kD; ++c) sd[c] = sb3::norm_sd(stats[kD + c], p->epsilon);
+    const double rsd = sb3::norm_sd(stats[2 * kD + 2], p->epsilon);
+    for (int k = 0; k < n * kD; ++k)
+        obs_out[k] = norm_obs ? sb3::norm_obs(obs[k], stats[k % kD], sd[k % kD], p->clip_obs) : obs[k];
+    for (int r = 0; r < n; ++r) {
+        if (reset) {
+            returns[r] = 0.0;
+            continue;
+        }
+        reward_out[r] = p->norm_reward ? sb3::norm_rew(reward[r], rsd, p->clip_reward) : reward[r];
+        const bool dn = done && done[r];
+        if (dn && terminal_obs && terminal_obs_out)
+            for (int c = 0; c < kD; ++c) {
+                const float x = terminal_obs[(size_t)r * kD + c];
+                terminal_obs_out[(size_t)r * kD + c] = norm_obs ? sb3::norm_obs(x, stats[c], sd[c], p->clip_obs) : x;
+            }
+        if (dn) returns[r] = 0.0;
+    }
+    return HE_OK;
 }
 
 }  // extern "C"

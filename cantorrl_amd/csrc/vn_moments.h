@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "../../include/hedge_env.h"
+#include "vn_sb3.h"
 
 namespace vn {
 
@@ -230,6 +231,7 @@ __device__ __forceinline__ double clip_d(double x, double lo, double hi) { retur
 
 struct ApplyArgs {
     int32_t norm_obs, norm_reward;
+    int32_t sb3;          // moments = HE_VN_MOMENTS_SB3: the f64 normalization of vn_sb3.h
     double clip_obs, clip_rew, eps;
     const double* stats;
     double* returns;
@@ -267,9 +269,18 @@ __device__ __forceinline__ FrozenPre load_frozen(const ApplyArgs& a, int64_t r, 
 struct FrozenNorm {
     ColNorm cn[kD];
     double rinv;
+    double m[kD], sd[kD], rsd;   // a.sb3: the columns' mean and sqrt(var + eps), the returns' sqrt(var + eps)
 };
 __device__ __forceinline__ void prep_frozen(FrozenNorm& z, const ApplyArgs& a, const FrozenPre& f) {
     const int t = threadIdx.x;
+    if (a.sb3) {   // uniform
+        if (t < kD) {
+            z.m[t] = f.m;
+            z.sd[t] = sb3::norm_sd(f.v, a.eps);
+        }
+        if (t == kD) z.rsd = sb3::norm_sd(f.v, a.eps);
+        return;
+    }
     if (t < kD) z.cn[t] = col_norm(f.m, f.v, a.eps);
     if (t == kD) z.rinv = 1.0 / sqrt(f.v + a.eps);
 }
@@ -288,21 +299,40 @@ __device__ __forceinline__ void apply_frozen_rows(const ApplyArgs& a, const Froz
     float* dst = a.obs_out + r0 * kD;
     const int nf = rows * kD;
     int c = t % kD;
+    const bool sb3n = a.sb3 && a.norm_obs;   // uniform: SB3's f64 (x - mean) / sqrt(var + eps)
+    if (sb3n) {
+#pragma unroll 1
+        for (int k = t; k < nf; k += kVnThreads) {
+            dst[k] = sb3::norm_obs(tile[k], z.m[c], z.sd[c], a.clip_obs);
+            c += kVnThreads % kD;
+            c = c >= kD ? c - kD : c;
+        }
+    } else {
 #pragma unroll
-    for (int q = 0; q < kD; ++q) {
-        const int k = t + q * kVnThreads;
-        if (k < nf) dst[k] = a.norm_obs ? norm_elem(tile[k], cn[c], clip) : tile[k];
-        c += kVnThreads % kD;
-        c = c >= kD ? c - kD : c;
+        for (int q = 0; q < kD; ++q) {
+            const int k = t + q * kVnThreads;
+            if (k < nf) dst[k] = a.norm_obs ? norm_elem(tile[k], cn[c], clip) : tile[k];
+            c += kVnThreads % kD;
+            c = c >= kD ? c - kD : c;
+        }
     }
     if (t >= rows) return;
     const int64_t r = r0 + t;
-    a.rew_out[r] = a.norm_reward ? (float)clip_d((double)rew * rinv, -a.clip_rew, a.clip_rew) : rew;
+    if (a.sb3)
+        a.rew_out[r] = a.norm_reward ? sb3::norm_rew(rew, z.rsd, a.clip_rew) : rew;
+    else
+        a.rew_out[r] = a.norm_reward ? (float)clip_d((double)rew * rinv, -a.clip_rew, a.clip_rew) : rew;
     if (done && tobs && a.tobs_out) {   // rare: per-row accesses (this thread stored the row)
+        if (sb3n) {
+#pragma unroll 1
+            for (int k = 0; k < kD; ++k)
+                a.tobs_out[r * kD + k] = sb3::norm_obs(tobs[r * kD + k], z.m[k], z.sd[k], a.clip_obs);
+        } else {
 #pragma unroll
-        for (int k = 0; k < kD; ++k) {
-            const float x = tobs[r * kD + k];
-            a.tobs_out[r * kD + k] = a.norm_obs ? norm_elem(x, cn[k], clip) : x;
+            for (int k = 0; k < kD; ++k) {
+                const float x = tobs[r * kD + k];
+                a.tobs_out[r * kD + k] = a.norm_obs ? norm_elem(x, cn[k], clip) : x;
+            }
         }
     }
     if (done) a.returns[r] = 0.0;   // self.returns[dones] = 0

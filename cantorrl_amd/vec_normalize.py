@@ -10,6 +10,10 @@ Monitor episode sums in device memory, updated by two kernels per step
 (cantorrl_amd/csrc/vecnorm.hip via he_vecnorm_step).  The obs, rewards and flags never
 leave the GPU on the tensor path (`reset_tensors` / `step_tensors`).
 
+`moments="sb3"` (up to 4,096 envs, e.g. the reference's N_ENVS = 2) reproduces SB3's NumPy
+arithmetic bit for bit instead of the default f64 batch moments (csrc/vn_sb3.h, one
+workgroup per step).
+
 Statistics are saved with `save(path)` as NPZ (no pickle) and restored with
 `DeviceVecNormalize.load(path, venv)`.
 """
@@ -24,7 +28,8 @@ from . import _lib
 from .vec_env import InfoView, _raw_stream
 
 # the attributes _params() reads: assigning one drops the cached step arguments
-_PARAM_ATTRS = frozenset(("training", "norm_obs", "norm_reward", "gamma", "clip_obs", "clip_reward", "epsilon"))
+_PARAM_ATTRS = frozenset(("training", "norm_obs", "norm_reward", "gamma", "clip_obs", "clip_reward", "epsilon",
+                          "moments"))
 
 
 class _RmsView:
@@ -36,7 +41,16 @@ class _RmsView:
 
 class DeviceVecNormalize:
     def __init__(self, venv, training=True, norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0,
-                 gamma=0.99, epsilon=1e-8):
+                 gamma=0.99, epsilon=1e-8, moments="f64"):
+        """moments: "f64" (default, any number of envs) takes the batch moments as f64 sums and
+        normalizes in f32; "sb3" (up to 4,096 envs) reproduces SB3's NumPy arithmetic bit for bit --
+        f32 row-order obs moments, pairwise f64 returns moments, f64 normalization -- in one
+        launch of one workgroup per step (csrc/vn_sb3.h)."""
+        if moments not in _lib.VN_MOMENTS:
+            raise ValueError(f"moments must be one of {sorted(_lib.VN_MOMENTS)}, not {moments!r}")
+        if moments == "sb3" and venv.num_envs > _lib.HE_VN_SB3_MAX_ENVS:
+            raise ValueError(f'moments="sb3" covers up to {_lib.HE_VN_SB3_MAX_ENVS} envs '
+                             f"(this env has {venv.num_envs}): use the default moments")
         self.venv = venv
         self.lib = _lib.load()
         self.num_envs = venv.num_envs
@@ -46,6 +60,7 @@ class DeviceVecNormalize:
         self.return_numpy = venv.return_numpy
         self.clip_obs, self.clip_reward, self.gamma, self.epsilon = clip_obs, clip_reward, gamma, epsilon
         self.training, self.norm_obs, self.norm_reward = training, norm_obs, norm_reward
+        self.moments = moments
         D, n, dev = _lib.HE_OBS_DIM, self.num_envs, self.device
         self._stats = torch.empty(int(self.lib.he_vecnorm_stats_len(D)), dtype=torch.float64, device=dev)
         self._scratch = torch.zeros(int(self.lib.he_vecnorm_scratch_bytes(n, D)), dtype=torch.uint8, device=dev)
@@ -92,6 +107,7 @@ class DeviceVecNormalize:
         p.training, p.norm_obs, p.norm_reward = int(self.training), int(self.norm_obs), int(self.norm_reward)
         p.gamma, p.clip_obs, p.clip_reward, p.epsilon = (float(self.gamma), float(self.clip_obs),
                                                            float(self.clip_reward), float(self.epsilon))
+        p.moments = _lib.VN_MOMENTS[self.moments]
         return p
 
     # ------------------------------------------------------------------ statistics (SB3 attributes)
@@ -137,7 +153,8 @@ class DeviceVecNormalize:
         """Running statistics and returns as host arrays (what VecNormalize pickles)."""
         return dict(stats=self._stats.cpu().numpy(), returns=self._returns.cpu().numpy(),
                     params=np.array([self.clip_obs, self.clip_reward, self.gamma, self.epsilon]),
-                    flags=np.array([self.training, self.norm_obs, self.norm_reward], np.int64))
+                    flags=np.array([self.training, self.norm_obs, self.norm_reward], np.int64),
+                    moments=np.array(self.moments))
 
     def set_state(self, st):
         self._stats.copy_(torch.as_tensor(np.asarray(st["stats"], np.float64)))
@@ -164,7 +181,8 @@ class DeviceVecNormalize:
         clip_obs, clip_reward, gamma, eps = (float(x) for x in z["params"])
         training, norm_obs, norm_reward = (bool(x) for x in z["flags"])
         obj = cls(venv, training=training, norm_obs=norm_obs, norm_reward=norm_reward, clip_obs=clip_obs,
-                  clip_reward=clip_reward, gamma=gamma, epsilon=eps)
+                  clip_reward=clip_reward, gamma=gamma, epsilon=eps,
+                  moments=str(z["moments"]) if "moments" in z else "f64")   # files from before the mode
         obj.set_state(z)
         return obj
 
@@ -191,7 +209,7 @@ class DeviceVecNormalize:
         c = self._args
         if c is None:
             key = (bool(self.training), bool(self.norm_obs), bool(self.norm_reward), float(self.gamma),
-                   float(self.clip_obs), float(self.clip_reward), float(self.epsilon))
+                   float(self.clip_obs), float(self.clip_reward), float(self.epsilon), self.moments)
             p = self._params()
             v = self.venv
             # Monitor's sums (venv monitor_keywords) add the env's f64 rewards (venv._rew64, the
@@ -246,7 +264,9 @@ class DeviceVecNormalize:
                 raise _lib.HedgeEnvError(f"he_vecnorm_attach_eval failed with status {st}: "
                                          f"{msg.decode() if msg else ''}")
             return "eval"
-        if not self._fusable:
+        # moments="sb3": row-order sums do not split into he_step's per-workgroup partials, so a
+        # training step is he_step + he_vecnorm_step (one workgroup)
+        if not self._fusable or p.moments != _lib.HE_VN_MOMENTS_F64:
             return False
         st = self.lib.he_vecnorm_attach(self.venv._h, pref, ptrs[4], ptrs[5], ptrs[6])
         # every build has the fused path and __init__ checked the env count, so any failure

@@ -383,7 +383,18 @@ he_status he_host_math(int32_t op, const double* x, int64_t count, double* out);
  * stats: device f64 [2 D + 4] = obs_mean[D], obs_var[D], obs_count, ret_mean, ret_var,
  * ret_count (RunningMeanStd(shape=(D,)) and RunningMeanStd(shape=())).  The batch
  * moments are one-pass f64 sums of shifted values per block, merged in block order
- * (deterministic). */
+ * (deterministic): moments = HE_VN_MOMENTS_F64, the default, for any n.
+ *
+ * moments = HE_VN_MOMENTS_SB3 (n <= 4096) reproduces SB3's own NumPy arithmetic bit for bit
+ * instead (oracle/vecnorm_oracle.py with moments="sb3"; cantorrl_amd/csrc/vn_sb3.h): the obs
+ * batch mean / variance as f32 sums in row order, the returns' by NumPy's pairwise f64 sum,
+ * and the normalization by an f64 subtract, sqrt and divide rounded to f32.  One launch of one
+ * workgroup per he_vecnorm_step / he_vecnorm_reset; he_vecnorm_attach refuses it (row-order
+ * sums do not split into per-workgroup partials), he_vecnorm_attach_eval honours it.  Any
+ * other value is HE_EINVAL. */
+#define HE_VN_MOMENTS_F64 0
+#define HE_VN_MOMENTS_SB3 1
+#define HE_VN_SB3_MAX_ENVS 4096
 typedef struct he_vecnorm_params {
     int32_t obs_dim;        /* D; 13 (HE_OBS_DIM) is the one supported */
     int32_t training;       /* update obs_rms / ret_rms / returns */
@@ -393,7 +404,8 @@ typedef struct he_vecnorm_params {
     double clip_obs;        /* 10.0 */
     double clip_reward;     /* 10.0 */
     double epsilon;         /* 1e-8 */
-    int32_t reserved[4];
+    int32_t moments;        /* HE_VN_MOMENTS_F64 (0) or HE_VN_MOMENTS_SB3 */
+    int32_t reserved[3];
 } he_vecnorm_params;
 
 /* Sizes of the device buffers the caller owns. */
@@ -464,6 +476,15 @@ he_status he_vecnorm_attach_eval(he_env* env, const he_vecnorm_params* p, const 
  * obs_out normalized (norm_obs, else a copy). */
 he_status he_vecnorm_reset(const he_vecnorm_params* p, int64_t n, const float* obs, double* returns,
                            double* stats, void* scratch, float* obs_out, void* stream);
+
+/* Host build of the HE_VN_MOMENTS_SB3 step (the same functions, cantorrl_amd/csrc/vn_sb3.h, run
+ * by one thread) on HOST pointers, for CPU tests of the summation orders: he_vecnorm_step's
+ * obs / reward / done / terminal_obs / returns / stats and outputs, no Monitor sums;
+ * reward = NULL is he_vecnorm_reset (reward_out, done and the terminal obs are then unused).
+ * p->moments is not read; n <= HE_VN_SB3_MAX_ENVS. */
+he_status he_host_vecnorm_sb3(const he_vecnorm_params* p, int64_t n, const float* obs, const float* reward,
+                              const uint8_t* done, const float* terminal_obs, double* returns, double* stats,
+                              float* obs_out, float* reward_out, float* terminal_obs_out);
 
 /* ---- Offline analytics over price paths -------------------------------------------
  * paths: device f64 [n_paths][n_cols] (row-major, the NPZ / .npy layout).
