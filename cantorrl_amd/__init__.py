@@ -6,6 +6,8 @@ reference's Python interface on top:
 
 * `HedgingVecEnv` -- N envs on one GPU, SB3 VecEnv interface (vec_env.py)
 * `HedgingEnv`    -- the single-env gym API with the reference ctor (env.py)
+* `RecurrentActor` -- a RecurrentPPO checkpoint's actor as one HIP kernel (agent.py,
+  include/hedge_actor.h, libhedgeactor.so), `HedgingVecEnv.evaluate_actor` around it
 """
 __version__ = "0.1.0"
 
@@ -17,4 +19,7 @@ def __getattr__(name):
     if name == "HedgingEnv":
         from .env import HedgingEnv
         return HedgingEnv
+    if name == "RecurrentActor":
+        from .agent import RecurrentActor
+        return RecurrentActor
     raise AttributeError(name)

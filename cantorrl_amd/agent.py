@@ -1,0 +1,314 @@
+"""RecurrentActor: the actor of an SB3 RecurrentPPO checkpoint on the device (libhedgeactor,
+include/hedge_actor.h): obs 13 -> LSTM 128 -> Linear 64 -> Linear 64 -> Linear 2, one HIP kernel
+per step for every env, the recurrent state resident on the device.
+
+    actor = RecurrentActor.from_sb3_zip("final_model.zip", normalization="normalization_stats.pkl")
+    records = venv.evaluate_actor(actor, num_episodes=1000)      # vec_env.HedgingVecEnv
+
+The arithmetic contract is in the header; `host_step` runs the same code compiled for the host
+(no GPU needed).  There is no torch fallback: a missing library is an error.
+"""
+import ctypes
+import io
+import os
+import pickle
+import zipfile
+
+import numpy as np
+
+from . import _lib
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(HERE, "lib", "libhedgeactor.so")
+HA_ABI_VERSION = 1
+OBS_DIM, HIDDEN, MLP, ACT_DIM = 13, 128, 64, 2
+ACTIVATIONS = {"tanh": 0, "relu": 1}
+SQUASHES = {"clip": 0, "tanh": 1}
+
+# state-dict key -> (ha_weights field, shape); the critic's keys are ignored
+ACTOR_KEYS = (
+    ("lstm_actor.weight_ih_l0", "w_ih", (4 * HIDDEN, OBS_DIM)),
+    ("lstm_actor.weight_hh_l0", "w_hh", (4 * HIDDEN, HIDDEN)),
+    ("lstm_actor.bias_ih_l0", "b_ih", (4 * HIDDEN,)),
+    ("lstm_actor.bias_hh_l0", "b_hh", (4 * HIDDEN,)),
+    ("mlp_extractor.policy_net.0.weight", "w1", (MLP, HIDDEN)),
+    ("mlp_extractor.policy_net.0.bias", "b1", (MLP,)),
+    ("mlp_extractor.policy_net.2.weight", "w2", (MLP, MLP)),
+    ("mlp_extractor.policy_net.2.bias", "b2", (MLP,)),
+    ("action_net.weight", "w3", (ACT_DIM, MLP)),
+    ("action_net.bias", "b3", (ACT_DIM,)),
+    ("log_std", "log_std", (ACT_DIM,)),
+)
+# the info columns ha_accumulate sums, in he_episode_record's order
+RECORD_INFO_KEYS = ("reward_step", "step_pnl_total", "raw_pnl_deviation_abs", "transaction_costs_total",
+                    "reward_pnl_component", "transaction_cost_penalty", "per_share_step_pnl")
+EPISODE_SUMS = np.dtype([("s", "<f8", (7,)), ("length", "<i8")])
+assert EPISODE_SUMS.itemsize == 64
+
+EXPORTS = ["ha_version", "ha_last_error", "ha_create", "ha_destroy", "ha_step", "ha_accumulate", "ha_host_step"]
+
+_F = ctypes.POINTER(ctypes.c_float)
+_D = ctypes.POINTER(ctypes.c_double)
+
+
+class HaWeights(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("abi_version", "obs_dim", "hidden", "n_lstm_layers", "mlp_width",
+                                               "act_dim", "activation", "squash", "has_clip", "reserved")] + \
+               [("clip_obs", ctypes.c_double), ("epsilon", ctypes.c_double)] + \
+               [(f, _F) for _, f, _ in ACTOR_KEYS] + [("obs_mean", _D), ("obs_var", _D)]
+
+
+_lib_ha = None
+
+
+def load(path=LIB_PATH):
+    """Load libhedgeactor (once).  Raises if the in-tree library is missing."""
+    global _lib_ha
+    if _lib_ha is not None:
+        return _lib_ha
+    if not os.path.exists(path):
+        raise _lib.HedgeEnvError(f"{path} not found: build it with `python -m cantorrl_amd.build` "
+                                 "(hipcc --offload-arch=gfx950).  There is no torch fallback.")
+    try:
+        import torch  # noqa: F401  (bind to torch's HIP runtime, as _lib.load)
+    except ImportError:
+        pass
+    lib = ctypes.CDLL(path)
+    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+    W = ctypes.POINTER(HaWeights)
+    sig = {
+        "ha_version": (ctypes.c_char_p, []),
+        "ha_last_error": (ctypes.c_char_p, [vp]),
+        "ha_create": (i32, [W, ctypes.POINTER(vp)]),
+        "ha_destroy": (i32, [vp]),
+        "ha_step": (i32, [vp, i64] + [vp] * 8),
+        "ha_accumulate": (i32, [vp, i64, i64] + [vp] * 10 + [i64, vp, vp]),
+        "ha_host_step": (i32, [W, i64] + [vp] * 7),
+    }
+    for name, (res, args) in sig.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _lib_ha = lib
+    return lib
+
+
+def _check(lib, handle, status, what):
+    if status != _lib.HE_OK:
+        msg = (lib.ha_last_error(handle) or b"").decode()
+        if status in (_lib.HE_ESHAPE, _lib.HE_EINVAL):
+            raise ValueError(f"{what}: {msg}")
+        raise _lib.HedgeEnvError(f"{what} failed (status {status}): {msg}")
+
+
+def _layer_indices(sd, prefix):
+    return sorted({k[len(prefix):].split("_l")[-1] for k in sd if k.startswith(prefix)})
+
+
+def weights_from_state_dict(sd):
+    """The 11 actor tensors of an SB3 RecurrentPPO state dict as contiguous f32 arrays, keyed by
+    ha_weights field; ValueError for any architecture but 13 -> LSTM 128 x 1 -> 64 -> 64 -> 2."""
+    layers = _layer_indices(sd, "lstm_actor.weight_ih")
+    if layers != ["0"]:
+        raise ValueError(f"lstm_actor has layers {layers}: only n_lstm_layers=1 is built")
+    extra = sorted(k for k in sd if k.startswith("mlp_extractor.policy_net.") and k.split(".")[2] not in ("0", "2"))
+    if extra:
+        raise ValueError(f"policy_net has layers beyond 64 -> 64: {extra}")
+    out = {}
+    for key, field, shape in ACTOR_KEYS:
+        if key not in sd:
+            raise ValueError(f"state dict has no {key!r}")
+        t = sd[key]
+        a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+        if tuple(a.shape) != shape:
+            raise ValueError(f"{key} has shape {tuple(a.shape)}, this actor is built for {shape} "
+                             "(obs 13, lstm_hidden_size 128, net_arch 64-64, 2 actions)")
+        out[field] = np.ascontiguousarray(a, dtype=np.float32)
+    return out
+
+
+def _normalization(norm):
+    """-> (obs_mean, obs_var, overrides) from a dict, a pickle path or a DeviceVecNormalize."""
+    if norm is None:
+        return None, None, {}
+    if isinstance(norm, (str, os.PathLike)):
+        with open(norm, "rb") as f:
+            norm = pickle.load(f)
+    if isinstance(norm, dict):
+        return norm["obs_mean"], norm["obs_var"], {}
+    rms = norm.obs_rms   # a DeviceVecNormalize (or anything with SB3 VecNormalize's attributes)
+    return rms.mean, rms.var, {"clip_obs": float(norm.clip_obs), "epsilon": float(norm.epsilon)}
+
+
+class RecurrentActor:
+    """The deterministic actor of a RecurrentPPO checkpoint.
+
+    weights: {field: array} (weights_from_state_dict) or a state dict.  obs_mean / obs_var (f64
+    [13]): VecNormalize's frozen statistics, applied as SB3 does (clip_obs=None: no clip, the
+    QuantConnect wrapper); without them the obs are used as they come (e.g. a DeviceVecNormalize
+    eval output).  activation: the MLP's ("tanh": SB3's default, "relu": model_wrapper.py);
+    squash: "clip" (SB3 predict) or "tanh" (model_wrapper.py)."""
+
+    def __init__(self, weights, obs_mean=None, obs_var=None, clip_obs=10.0, epsilon=1e-8, activation="tanh",
+                 squash="clip", device="cuda:0"):
+        if any("." in k for k in weights):
+            weights = weights_from_state_dict(weights)
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}, not {activation!r}")
+        if squash not in SQUASHES:
+            raise ValueError(f"squash must be one of {sorted(SQUASHES)}, not {squash!r}")
+        self.lib = load()
+        self._arrays = {}
+        for _, field, shape in ACTOR_KEYS:
+            a = np.ascontiguousarray(weights[field], dtype=np.float32)
+            if a.shape != shape:
+                raise ValueError(f"{field} has shape {a.shape}, expected {shape}")
+            self._arrays[field] = a
+        if (obs_mean is None) != (obs_var is None):
+            raise ValueError("obs_mean and obs_var come together")
+        w = HaWeights()
+        w.abi_version = HA_ABI_VERSION
+        w.obs_dim, w.hidden, w.n_lstm_layers, w.mlp_width, w.act_dim = OBS_DIM, HIDDEN, 1, MLP, ACT_DIM
+        w.activation, w.squash = ACTIVATIONS[activation], SQUASHES[squash]
+        w.has_clip = 0 if clip_obs is None else 1
+        w.clip_obs = 0.0 if clip_obs is None else float(clip_obs)
+        w.epsilon = float(epsilon)
+        for _, field, _s in ACTOR_KEYS:
+            setattr(w, field, self._arrays[field].ctypes.data_as(_F))
+        if obs_mean is not None:
+            for name, v in (("obs_mean", obs_mean), ("obs_var", obs_var)):
+                a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
+                if a.shape != (OBS_DIM,):
+                    raise ValueError(f"{name} has {a.size} entries, the obs has {OBS_DIM}")
+                self._arrays[name] = a
+                setattr(w, name, a.ctypes.data_as(_D))
+        self._w = w
+        self.activation, self.squash = activation, squash
+        self.clip_obs, self.epsilon = clip_obs, float(epsilon)
+        self.device_name = device
+        self._h = None          # ha_actor*, made with the first device call
+        self.device = None
+        self.h = self.c = None  # [n, 128] device tensors (reset_states)
+        self._sums = None
+
+    # ------------------------------------------------------------------ loaders
+    @classmethod
+    def from_state_dict(cls, sd, normalization=None, **kw):
+        mean, var, over = _normalization(normalization)
+        return cls(weights_from_state_dict(sd), obs_mean=mean, obs_var=var, **dict(over, **kw))
+
+    @classmethod
+    def from_sb3_zip(cls, path, normalization=None, **kw):
+        """An SB3 `model.save()` zip: its policy.pth is a plain torch state dict."""
+        import torch
+        with zipfile.ZipFile(path) as z:
+            sd = torch.load(io.BytesIO(z.read("policy.pth")), map_location="cpu", weights_only=True)
+        return cls.from_state_dict(sd, normalization=normalization, **kw)
+
+    # ------------------------------------------------------------------ device
+    def _handle(self):
+        if self._h is None:
+            import torch
+            dev = torch.device(self.device_name)
+            if dev.type != "cuda" or not torch.cuda.is_available():
+                raise _lib.HedgeEnvError("RecurrentActor.step runs on a HIP device (cuda:N); host_step is the CPU build")
+            dev = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
+            h = ctypes.c_void_p()
+            with torch.cuda.device(dev):
+                _check(self.lib, None, self.lib.ha_create(ctypes.byref(self._w), ctypes.byref(h)), "ha_create")
+            self._h, self.device = h, dev
+        return self._h
+
+    def reset_states(self, n_envs):
+        """Zero h, c (and the episode sums) for n_envs envs."""
+        import torch
+        self._handle()
+        n = int(n_envs)
+        if self.h is None or self.h.shape[0] != n:
+            self.h = torch.zeros((n, HIDDEN), dtype=torch.float32, device=self.device)
+            self.c = torch.zeros((n, HIDDEN), dtype=torch.float32, device=self.device)
+            self._sums = torch.zeros((n, EPISODE_SUMS.itemsize), dtype=torch.uint8, device=self.device)
+        else:
+            self.h.zero_()
+            self.c.zero_()
+            self._sums.zero_()
+        return self.h, self.c
+
+    def _stream(self):
+        from .vec_env import _raw_stream
+        return _raw_stream(self.device.index)
+
+    def step(self, obs, episode_start, out=None, mean_out=None, obs_norm_out=None):
+        """obs [n,13] f32, episode_start [n] u8 / bool device tensors -> actions [n,2]; h, c are
+        updated in place.  Enqueued on the current stream, no host sync."""
+        import torch
+        h = self._handle()
+        n = int(obs.shape[0])
+        if self.h is None or self.h.shape[0] != n:
+            self.reset_states(n)
+        if obs.dtype != torch.float32 or not obs.is_contiguous() or obs.device != self.device or obs.shape[1] != OBS_DIM:
+            raise ValueError(f"obs must be a contiguous float32 [n, {OBS_DIM}] tensor on {self.device}")
+        if episode_start.dtype == torch.bool:
+            episode_start = episode_start.view(torch.uint8)
+        if episode_start.dtype != torch.uint8 or episode_start.numel() != n or not episode_start.is_contiguous():
+            raise ValueError("episode_start must be a contiguous uint8 / bool [n] tensor")
+        if out is None:
+            out = torch.empty((n, ACT_DIM), dtype=torch.float32, device=self.device)
+        for t, w in ((out, ACT_DIM), (mean_out, ACT_DIM), (obs_norm_out, OBS_DIM)):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n * w):
+                raise ValueError("output tensors must be contiguous float32 of the step's shape")
+        st = self.lib.ha_step(h, n, obs.data_ptr(), episode_start.data_ptr(), self.h.data_ptr(), self.c.data_ptr(),
+                              out.data_ptr(), None if mean_out is None else mean_out.data_ptr(),
+                              None if obs_norm_out is None else obs_norm_out.data_ptr(), self._stream())
+        _check(self.lib, h, st, "ha_step")
+        return out
+
+    def accumulate(self, info, terminated, records, record_count, env_id_offset=0):
+        """One env step's info columns ({key: f64 [n] device tensor}, RECORD_INFO_KEYS) into the
+        per-env episode sums; envs with `terminated` set append an EPISODE_RECORD row to
+        `records` (uint8 [cap, 80]) at `record_count` (int64 [1]) and restart their sums."""
+        h = self._handle()
+        n = int(terminated.numel())
+        cols = [info[k].data_ptr() for k in RECORD_INFO_KEYS]
+        cap = 0 if records is None else int(records.shape[0])
+        st = self.lib.ha_accumulate(h, n, int(env_id_offset), *cols, terminated.data_ptr(), self._sums.data_ptr(),
+                                    None if records is None else records.data_ptr(), cap, record_count.data_ptr(),
+                                    self._stream())
+        _check(self.lib, h, st, "ha_accumulate")
+
+    # ------------------------------------------------------------------ host
+    def host_step(self, obs, episode_start, h, c, mean_out=None, obs_norm_out=None):
+        """ha_host_step over NumPy: obs [n,13] f32, episode_start [n], h / c [n,128] f32 C-contiguous
+        arrays updated IN PLACE; returns actions [n,2].  The device kernel's arithmetic on the CPU."""
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        n = obs.shape[0]
+        es = np.ascontiguousarray(np.asarray(episode_start).reshape(-1), dtype=np.uint8)
+        for name, a in (("h", h), ("c", c)):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous
+                    and a.shape == (n, HIDDEN)):
+                raise ValueError(f"{name} must be a C-contiguous float32 [{n}, {HIDDEN}] array")
+        if obs.shape != (n, OBS_DIM) or es.shape != (n,):
+            raise ValueError(f"obs must be [n, {OBS_DIM}] and episode_start [n]")
+        act = np.empty((n, ACT_DIM), np.float32)
+        for a, w in ((mean_out, ACT_DIM), (obs_norm_out, OBS_DIM)):
+            if a is not None and not (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (n, w)):
+                raise ValueError("mean_out / obs_norm_out must be C-contiguous float32 of the step's shape")
+        st = self.lib.ha_host_step(ctypes.byref(self._w), n, obs.ctypes.data, es.ctypes.data, h.ctypes.data,
+                                   c.ctypes.data, act.ctypes.data, None if mean_out is None else mean_out.ctypes.data,
+                                   None if obs_norm_out is None else obs_norm_out.ctypes.data)
+        _check(self.lib, None, st, "ha_host_step")
+        return act
+
+    def close(self):
+        if self._h is not None:
+            import torch
+            torch.cuda.synchronize(self.device)
+            self.lib.ha_destroy(self._h)
+            self._h = None
+        self.h = self.c = self._sums = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1,5 +1,6 @@
-"""Build the gfx950 libraries in-tree: cantorrl_amd/lib/libhedgeenv.so (the env) and
-cantorrl_amd/lib/librbergomi.so (the rough-Bergomi data generator), plus the host-only
+"""Build the gfx950 libraries in-tree: cantorrl_amd/lib/libhedgeenv.so (the env),
+cantorrl_amd/lib/librbergomi.so (the rough-Bergomi data generator) and
+cantorrl_amd/lib/libhedgeactor.so (the RecurrentPPO actor), plus the host-only
 CPython module cantorrl_amd/lib/_info_rows*.so (a step's SB3 info dicts, csrc/info_rows.c).
 
     python -m cantorrl_amd.build [--force]
@@ -42,7 +43,13 @@ RB_OUT = os.path.join(HERE, "lib", "librbergomi.so")
 VN_SRC = os.path.join(HERE, "csrc", "vecnorm.hip")
 AN_SRC = os.path.join(HERE, "csrc", "analytics.hip")
 DEPS = DEPS + [VN_SRC, AN_SRC, os.path.join(HERE, "csrc", "vn_moments.h"), os.path.join(HERE, "csrc", "vn_sb3.h")]
-TARGETS = [([SRC, VN_SRC, AN_SRC], DEPS, OUT, ENV_FLAGS), ([RB_SRC], RB_DEPS, RB_OUT, [])]
+# the RecurrentPPO actor (include/hedge_actor.h): its own library, the plain FLAGS
+HA_SRC = os.path.join(HERE, "csrc", "hedge_actor.hip")
+HA_DEPS = [HA_SRC, os.path.join(HERE, "csrc", "ha_math.h"), os.path.join(HERE, "csrc", "he_math.h"),
+           os.path.join(REPO, "include", "hedge_actor.h"), os.path.join(REPO, "include", "hedge_env.h")]
+HA_OUT = os.path.join(HERE, "lib", "libhedgeactor.so")
+TARGETS = [([SRC, VN_SRC, AN_SRC], DEPS, OUT, ENV_FLAGS), ([RB_SRC], RB_DEPS, RB_OUT, []),
+           ([HA_SRC], HA_DEPS, HA_OUT, [])]
 
 
 # host-only: the CPython module that builds a step's SB3 info dicts (csrc/info_rows.c)

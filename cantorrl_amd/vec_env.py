@@ -274,6 +274,9 @@ class HedgingVecEnv:
             host_io = self.return_numpy and n <= HOST_IO_MAX_ENVS
         self._hio = _HostIo(self) if host_io else None
         self._ep_ret_h = np.zeros(n, np.float64)
+        # rollout_actor: (actor, its episode_start flags) of the running closed loop
+        self._actor_start = None
+        self._actor_cnt = torch.zeros(1, dtype=torch.int64, device=dev)
 
         if self.return_numpy:
             # the host path's pinned blocks (step outputs, actions, the episode-end pull), made
@@ -408,6 +411,8 @@ class HedgingVecEnv:
         by the env's own PCG64 stream -- one per env in env_ids order (all envs when env_ids
         is None)."""
         self._retire_view()
+        if env_ids is None:
+            self._actor_start = None   # rollout_actor: every env begins an episode
         if self._pending_seeds is not None:
             self.seed_envs(self._pending_seeds)
             self._pending_seeds = None
@@ -613,6 +618,73 @@ class HedgingVecEnv:
             steps += chunk
             done = int(cnt.item())
             if done >= num_episodes or steps >= limit:
+                break
+        n = min(int(cnt.item()), cap)
+        out = recs[:n].cpu().numpy().view(_lib.EPISODE_RECORD).reshape(n)
+        return out[:num_episodes]
+
+    def _actor_info_check(self):
+        from .agent import RECORD_INFO_KEYS
+        missing = [k for k in RECORD_INFO_KEYS if k not in self._info_t]
+        if missing:
+            raise ValueError(f"the actor's episode records need the info columns {missing} in info_keys")
+
+    def rollout_actor(self, actor, k_steps, actions_out=None, obs=None, reward=None, terminated=None,
+                      records=None, record_count=None):
+        """k_steps closed-loop steps driven by a RecurrentActor (agent.py): per step ha_step on the
+        current obs and the last step's `terminated` (ones after a reset), he_step, ha_accumulate,
+        all enqueued on the current stream with no host sync.  actions_out [K,N,2], obs [K,N,13],
+        reward [K,N], terminated [K,N] are filled as `rollout` fills them (each may be None).
+        Finished episodes append EPISODE_RECORD rows to `records` (uint8 [cap, 80]) at
+        `record_count` (int64 [1]); their sums are those of the step's f64 info columns, so the
+        env needs agent.RECORD_INFO_KEYS in info_keys."""
+        self._actor_info_check()
+        K = int(k_steps)
+        n = self.num_envs
+        for name, t, shape in (("actions_out", actions_out, (K, n, 2)), ("obs", obs, (K, n, 13)),
+                               ("reward", reward, (K, n)), ("terminated", terminated, (K, n))):
+            if t is not None and (tuple(t.shape) != shape or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous tensor of shape {shape}")
+        st = self._actor_start
+        if st is None or st[0] is not actor or actor.h is None or actor.h.shape[0] != n:
+            # a new pairing (or the env was reset): every env begins an episode
+            actor.reset_states(n)
+            start = torch.ones(n, dtype=torch.uint8, device=self.device)
+            self._actor_start = st = (actor, start)
+        start = st[1]
+        if record_count is None:
+            record_count = self._actor_cnt
+        act = self._act
+        for k in range(K):
+            a = actions_out[k] if actions_out is not None else act
+            actor.step(self._obs, start, out=a)
+            o, r, t, _ = self.step_tensors(a, terminal_obs=False)
+            actor.accumulate(self._info_t, t, records, record_count, self._cfg.global_env_offset)
+            start.copy_(t)
+            if obs is not None:
+                obs[k].copy_(o)
+            if reward is not None:
+                reward[k].copy_(r)
+            if terminated is not None:
+                terminated[k].copy_(t)
+
+    def evaluate_actor(self, actor, num_episodes, chunk=64, max_steps=None):
+        """Run `actor` in closed loop until `num_episodes` episodes finished (all envs stepping)
+        and return exactly that many EPISODE_RECORD rows: run_evaluation's loop
+        (train_ppo_v2.py:415-576) on the device; evaluation.py turns the rows into its
+        mean / std / CVaR95."""
+        dev = self.device
+        cap = int(num_episodes) + self.num_envs
+        recs = torch.zeros((cap, _lib.EPISODE_RECORD.itemsize), dtype=torch.uint8, device=dev)
+        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._actor_info_check()
+        self.reset_tensors()
+        steps = 0
+        limit = max_steps if max_steps is not None else (num_episodes // self.num_envs + 2) * (self.episode_length + 1)
+        while True:
+            self.rollout_actor(actor, chunk, records=recs, record_count=cnt)
+            steps += chunk
+            if int(cnt.item()) >= num_episodes or steps >= limit:
                 break
         n = min(int(cnt.item()), cap)
         out = recs[:n].cpu().numpy().view(_lib.EPISODE_RECORD).reshape(n)
