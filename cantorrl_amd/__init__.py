@@ -8,6 +8,8 @@ reference's Python interface on top:
 * `HedgingEnv`    -- the single-env gym API with the reference ctor (env.py)
 * `RecurrentActor` -- a RecurrentPPO checkpoint's actor as one HIP kernel (agent.py,
   include/hedge_actor.h, libhedgeactor.so), `HedgingVecEnv.evaluate_actor` around it
+* `RecurrentPolicy`, `RolloutCollector` -- actor + critic + sampling + log-prob per step in one
+  kernel and GAE: RecurrentPPO's collect_rollouts on the device (agent.py, collect.py)
 """
 __version__ = "0.1.0"
 
@@ -22,4 +24,10 @@ def __getattr__(name):
     if name == "RecurrentActor":
         from .agent import RecurrentActor
         return RecurrentActor
+    if name == "RecurrentPolicy":
+        from .agent import RecurrentPolicy
+        return RecurrentPolicy
+    if name == "RolloutCollector":
+        from .collect import RolloutCollector
+        return RolloutCollector
     raise AttributeError(name)

@@ -5,6 +5,12 @@ per step for every env, the recurrent state resident on the device.
     actor = RecurrentActor.from_sb3_zip("final_model.zip", normalization="normalization_stats.pkl")
     records = venv.evaluate_actor(actor, num_episodes=1000)      # vec_env.HedgingVecEnv
 
+RecurrentPolicy is the training-side counterpart: actor and critic (its own LSTM 128 -> 64 -> 64
+-> 1), the sampled action, the value and the log-probability of a rollout step in one launch, and
+GAE; collect.RolloutCollector fills a rollout buffer with it.
+
+    policy = RecurrentPolicy.from_sb3_zip("final_model.zip")
+
 The arithmetic contract is in the header; `host_step` runs the same code compiled for the host
 (no GPU needed).  There is no torch fallback: a missing library is an error.
 """
@@ -25,7 +31,7 @@ OBS_DIM, HIDDEN, MLP, ACT_DIM = 13, 128, 64, 2
 ACTIVATIONS = {"tanh": 0, "relu": 1}
 SQUASHES = {"clip": 0, "tanh": 1}
 
-# state-dict key -> (ha_weights field, shape); the critic's keys are ignored
+# state-dict key -> (ha_weights field, shape); RecurrentActor ignores the critic's keys
 ACTOR_KEYS = (
     ("lstm_actor.weight_ih_l0", "w_ih", (4 * HIDDEN, OBS_DIM)),
     ("lstm_actor.weight_hh_l0", "w_hh", (4 * HIDDEN, HIDDEN)),
@@ -45,7 +51,25 @@ RECORD_INFO_KEYS = ("reward_step", "step_pnl_total", "raw_pnl_deviation_abs", "t
 EPISODE_SUMS = np.dtype([("s", "<f8", (7,)), ("length", "<i8")])
 assert EPISODE_SUMS.itemsize == 64
 
-EXPORTS = ["ha_version", "ha_last_error", "ha_create", "ha_destroy", "ha_step", "ha_accumulate", "ha_host_step"]
+# the critic of the same checkpoint (RecurrentPolicy): state-dict key -> (ha_policy_weights field, shape)
+CRITIC_KEYS = (
+    ("lstm_critic.weight_ih_l0", "c_w_ih", (4 * HIDDEN, OBS_DIM)),
+    ("lstm_critic.weight_hh_l0", "c_w_hh", (4 * HIDDEN, HIDDEN)),
+    ("lstm_critic.bias_ih_l0", "c_b_ih", (4 * HIDDEN,)),
+    ("lstm_critic.bias_hh_l0", "c_b_hh", (4 * HIDDEN,)),
+    ("mlp_extractor.value_net.0.weight", "v1", (MLP, HIDDEN)),
+    ("mlp_extractor.value_net.0.bias", "vb1", (MLP,)),
+    ("mlp_extractor.value_net.2.weight", "v2", (MLP, MLP)),
+    ("mlp_extractor.value_net.2.bias", "vb2", (MLP,)),
+    ("value_net.weight", "v3", (1, MLP)),
+    ("value_net.bias", "vb3", (1,)),
+)
+POLICY_KEYS = ACTOR_KEYS + CRITIC_KEYS
+HA_POLICY_ABI_VERSION = 1
+
+EXPORTS = ["ha_version", "ha_last_error", "ha_create", "ha_destroy", "ha_step", "ha_accumulate", "ha_host_step",
+           "ha_policy_last_error", "ha_policy_create", "ha_policy_destroy", "ha_policy_update", "ha_policy_step",
+           "ha_gae", "ha_host_policy_step", "ha_host_gae"]
 
 _F = ctypes.POINTER(ctypes.c_float)
 _D = ctypes.POINTER(ctypes.c_double)
@@ -56,6 +80,13 @@ class HaWeights(ctypes.Structure):
                                                "act_dim", "activation", "squash", "has_clip", "reserved")] + \
                [("clip_obs", ctypes.c_double), ("epsilon", ctypes.c_double)] + \
                [(f, _F) for _, f, _ in ACTOR_KEYS] + [("obs_mean", _D), ("obs_var", _D)]
+
+
+class HaPolicyWeights(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("abi_version", "obs_dim", "hidden", "n_lstm_layers", "mlp_width",
+                                               "act_dim", "activation", "has_clip")] + \
+               [("clip_obs", ctypes.c_double), ("epsilon", ctypes.c_double), ("obs_mean", _D), ("obs_var", _D)] + \
+               [(f, _F) for _, f, _ in POLICY_KEYS]
 
 
 _lib_ha = None
@@ -75,7 +106,8 @@ def load(path=LIB_PATH):
         pass
     lib = ctypes.CDLL(path)
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    W = ctypes.POINTER(HaWeights)
+    u64, f64 = ctypes.c_uint64, ctypes.c_double
+    W, PW = ctypes.POINTER(HaWeights), ctypes.POINTER(HaPolicyWeights)
     sig = {
         "ha_version": (ctypes.c_char_p, []),
         "ha_last_error": (ctypes.c_char_p, [vp]),
@@ -84,6 +116,14 @@ def load(path=LIB_PATH):
         "ha_step": (i32, [vp, i64] + [vp] * 8),
         "ha_accumulate": (i32, [vp, i64, i64] + [vp] * 10 + [i64, vp, vp]),
         "ha_host_step": (i32, [W, i64] + [vp] * 7),
+        "ha_policy_last_error": (ctypes.c_char_p, [vp]),
+        "ha_policy_create": (i32, [PW, ctypes.POINTER(vp)]),
+        "ha_policy_destroy": (i32, [vp]),
+        "ha_policy_update": (i32, [vp, PW]),
+        "ha_policy_step": (i32, [vp, i64, i64, u64, u64, i32, i32] + [vp] * 13),
+        "ha_gae": (i32, [i64, i64, f64, f64] + [vp] * 8),
+        "ha_host_policy_step": (i32, [PW, i64, i64, u64, u64, i32, i32] + [vp] * 12),
+        "ha_host_gae": (i32, [i64, i64, f64, f64] + [vp] * 7),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -306,6 +346,280 @@ class RecurrentActor:
             self.lib.ha_destroy(self._h)
             self._h = None
         self.h = self.c = self._sums = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def policy_weights_from_state_dict(sd):
+    """The actor's 11 and the critic's 10 tensors of an SB3 RecurrentPPO state dict, keyed by
+    ha_policy_weights field.  ValueError unless the critic has its own LSTM (sb3_contrib's default,
+    enable_critic_lstm=True and shared_lstm=False) of the actor's shape."""
+    out = weights_from_state_dict(sd)
+    if not any(k.startswith("lstm_critic.") for k in sd):
+        raise ValueError("state dict has no lstm_critic.*: RecurrentPolicy is built for a critic with its own LSTM "
+                         "(enable_critic_lstm=True, shared_lstm=False); shared_lstm=True and a critic without an "
+                         "LSTM (enable_critic_lstm=False) are not")
+    layers = _layer_indices(sd, "lstm_critic.weight_ih")
+    if layers != ["0"]:
+        raise ValueError(f"lstm_critic has layers {layers}: only n_lstm_layers=1 is built")
+    extra = sorted(k for k in sd if k.startswith("mlp_extractor.value_net.") and k.split(".")[2] not in ("0", "2"))
+    if extra:
+        raise ValueError(f"value_net has layers beyond 64 -> 64: {extra}")
+    for key, field, shape in CRITIC_KEYS:
+        if key not in sd:
+            raise ValueError(f"state dict has no {key!r}")
+        t = sd[key]
+        a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+        if tuple(a.shape) != shape:
+            raise ValueError(f"{key} has shape {tuple(a.shape)}, this critic is built for {shape} "
+                             "(obs 13, lstm_hidden_size 128, net_arch 64-64, 1 value)")
+        out[field] = np.ascontiguousarray(a, dtype=np.float32)
+    return out
+
+
+STATE_NAMES = ("h_pi", "c_pi", "h_vf", "c_vf")
+# ha_policy_step's outputs: name -> trailing shape
+STEP_OUTPUTS = (("actions", (ACT_DIM,)), ("env_actions", (ACT_DIM,)), ("values", ()), ("log_probs", ()),
+                ("mean", (ACT_DIM,)), ("obs_norm", (OBS_DIM,)))
+_REQUIRED_OUT = ("actions", "env_actions", "values", "log_probs")
+
+
+class RecurrentPolicy:
+    """Actor and critic of a RecurrentPPO checkpoint for rollout collection (collect.RolloutCollector):
+    per step the sampled action, its clipped form, the value and the log-probability of every env in
+    one kernel launch (ha_policy_step), and GAE over the filled buffer (ha_gae).
+
+    weights: {field: array} (policy_weights_from_state_dict) or a state dict.  obs_mean / obs_var,
+    clip_obs, epsilon, activation: as RecurrentActor; leave the statistics out when the env is a
+    DeviceVecNormalize, whose obs are normalised already.  The four LSTM states live on the device
+    as h_pi, c_pi, h_vf, c_vf [n, 128]."""
+
+    def __init__(self, weights, obs_mean=None, obs_var=None, clip_obs=10.0, epsilon=1e-8, activation="tanh",
+                 device="cuda:0"):
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}, not {activation!r}")
+        if (obs_mean is None) != (obs_var is None):
+            raise ValueError("obs_mean and obs_var come together")
+        self.lib = load()
+        self._arrays = {}
+        w = HaPolicyWeights()
+        w.abi_version = HA_POLICY_ABI_VERSION
+        w.obs_dim, w.hidden, w.n_lstm_layers, w.mlp_width, w.act_dim = OBS_DIM, HIDDEN, 1, MLP, ACT_DIM
+        w.activation = ACTIVATIONS[activation]
+        w.has_clip = 0 if clip_obs is None else 1
+        w.clip_obs = 0.0 if clip_obs is None else float(clip_obs)
+        w.epsilon = float(epsilon)
+        self._w = w
+        self._set_tensors(weights)
+        if obs_mean is not None:
+            for name, v in (("obs_mean", obs_mean), ("obs_var", obs_var)):
+                a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
+                if a.shape != (OBS_DIM,):
+                    raise ValueError(f"{name} has {a.size} entries, the obs has {OBS_DIM}")
+                self._arrays[name] = a
+                setattr(w, name, a.ctypes.data_as(_D))
+        self.activation = activation
+        self.clip_obs, self.epsilon = clip_obs, float(epsilon)
+        self.device_name = device
+        self._h = None          # ha_policy*, made with the first device call
+        self.device = None
+        self.h_pi = self.c_pi = self.h_vf = self.c_vf = None
+
+    def _set_tensors(self, weights):
+        if any("." in k for k in weights):
+            weights = policy_weights_from_state_dict(weights)
+        arrays = {}
+        for _, field, shape in POLICY_KEYS:
+            a = np.ascontiguousarray(weights[field], dtype=np.float32)
+            if a.shape != shape:
+                raise ValueError(f"{field} has shape {a.shape}, expected {shape}")
+            arrays[field] = a
+        self._arrays.update(arrays)   # the struct points into these: they live as long as it does
+        for field, a in arrays.items():
+            setattr(self._w, field, a.ctypes.data_as(_F))
+
+    # ------------------------------------------------------------------ loaders
+    @classmethod
+    def from_state_dict(cls, sd, normalization=None, **kw):
+        mean, var, over = _normalization(normalization)
+        return cls(policy_weights_from_state_dict(sd), obs_mean=mean, obs_var=var, **dict(over, **kw))
+
+    @classmethod
+    def from_sb3_zip(cls, path, normalization=None, **kw):
+        """An SB3 `model.save()` zip: its policy.pth is a plain torch state dict."""
+        import torch
+        with zipfile.ZipFile(path) as z:
+            sd = torch.load(io.BytesIO(z.read("policy.pth")), map_location="cpu", weights_only=True)
+        return cls.from_state_dict(sd, normalization=normalization, **kw)
+
+    def load_state_dict(self, sd):
+        """New tensors (a state dict or {field: array}) after a PPO update: ha_policy_update re-packs
+        and re-uploads them into the existing handle.  Waits for the device; the LSTM states stay."""
+        self._set_tensors(sd)
+        if self._h is not None:
+            import torch
+            with torch.cuda.device(self.device):
+                st = self.lib.ha_policy_update(self._h, ctypes.byref(self._w))
+            self._check(self._h, st, "ha_policy_update")
+
+    def _check(self, handle, status, what):
+        if status != _lib.HE_OK:
+            msg = (self.lib.ha_policy_last_error(handle) or b"").decode()
+            if status in (_lib.HE_ESHAPE, _lib.HE_EINVAL):
+                raise ValueError(f"{what}: {msg}")
+            raise _lib.HedgeEnvError(f"{what} failed (status {status}): {msg}")
+
+    # ------------------------------------------------------------------ device
+    def _handle(self):
+        if self._h is None:
+            import torch
+            dev = torch.device(self.device_name)
+            if dev.type != "cuda" or not torch.cuda.is_available():
+                raise _lib.HedgeEnvError("RecurrentPolicy.step runs on a HIP device (cuda:N); host_step is the CPU build")
+            dev = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
+            h = ctypes.c_void_p()
+            with torch.cuda.device(dev):
+                self._check(None, self.lib.ha_policy_create(ctypes.byref(self._w), ctypes.byref(h)), "ha_policy_create")
+            self._h, self.device = h, dev
+        return self._h
+
+    def _stream(self):
+        from .vec_env import _raw_stream
+        return _raw_stream(self.device.index)
+
+    @property
+    def states(self):
+        return tuple(getattr(self, k) for k in STATE_NAMES)
+
+    def reset_states(self, n_envs):
+        """Zero the four LSTM states for n_envs envs; returns (h_pi, c_pi, h_vf, c_vf)."""
+        import torch
+        self._handle()
+        n = int(n_envs)
+        if self.h_pi is None or self.h_pi.shape[0] != n:
+            for k in STATE_NAMES:
+                setattr(self, k, torch.zeros((n, HIDDEN), dtype=torch.float32, device=self.device))
+        else:
+            for t in self.states:
+                t.zero_()
+        return self.states
+
+    def step(self, obs, episode_start, seed, step_index, deterministic=False, write_state=True, env_id_offset=0,
+             out=None):
+        """One collection step: obs [n,13] f32, episode_start [n] u8 / bool device tensors ->
+        {"actions", "env_actions" [n,2], "values", "log_probs" [n]} (and "mean" [n,2], "obs_norm"
+        [n,13] where `out` has them).  `out`: a dict of preallocated contiguous f32 tensors to write
+        into, e.g. the [k] slices of a rollout buffer.  The noise of env e is a function of (seed,
+        step_index, env_id_offset + e) alone.  write_state=False leaves the LSTM states as they are
+        (SB3's predict_values).  Enqueued on the current stream, no host sync."""
+        import torch
+        h = self._handle()
+        n = int(obs.shape[0])
+        if self.h_pi is None or self.h_pi.shape[0] != n:
+            self.reset_states(n)
+        if obs.dtype != torch.float32 or not obs.is_contiguous() or obs.device != self.device or obs.shape[1] != OBS_DIM:
+            raise ValueError(f"obs must be a contiguous float32 [n, {OBS_DIM}] tensor on {self.device}")
+        if episode_start.dtype == torch.bool:
+            episode_start = episode_start.view(torch.uint8)
+        if episode_start.dtype != torch.uint8 or episode_start.numel() != n or not episode_start.is_contiguous():
+            raise ValueError("episode_start must be a contiguous uint8 / bool [n] tensor")
+        res = dict(out) if out else {}
+        ptr = []
+        for name, tail in STEP_OUTPUTS:
+            t = res.get(name)
+            if t is None and name in _REQUIRED_OUT:
+                t = res[name] = torch.empty((n,) + tail, dtype=torch.float32, device=self.device)
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device
+                                  or t.numel() != n * int(np.prod(tail, dtype=np.int64))):
+                raise ValueError(f"out[{name!r}] must be a contiguous float32 tensor of {n} x {tail} on {self.device}")
+            ptr.append(None if t is None else t.data_ptr())
+        st = self.lib.ha_policy_step(h, n, int(env_id_offset), int(seed) & (2 ** 64 - 1), int(step_index),
+                                     int(bool(deterministic)), int(bool(write_state)), obs.data_ptr(),
+                                     episode_start.data_ptr(), *(t.data_ptr() for t in self.states), *ptr,
+                                     self._stream())
+        self._check(h, st, "ha_policy_step")
+        return res
+
+    def gae(self, rewards, values, episode_starts, last_values, last_dones, gamma, gae_lambda, advantages=None,
+            returns=None):
+        """SB3's compute_returns_and_advantage over [K,N] device tensors (ha_gae) ->
+        (advantages, returns) [K,N] f32.  No host sync."""
+        import torch
+        self._handle()
+        K, n = (int(x) for x in rewards.shape)
+        if advantages is None:
+            advantages = torch.empty((K, n), dtype=torch.float32, device=self.device)
+        if returns is None:
+            returns = torch.empty((K, n), dtype=torch.float32, device=self.device)
+        u8 = []
+        for t in (episode_starts, last_dones):
+            u8.append(t.view(torch.uint8) if t.dtype == torch.bool else t)
+        for name, t, dt, numel in (("rewards", rewards, torch.float32, K * n), ("values", values, torch.float32, K * n),
+                                   ("episode_starts", u8[0], torch.uint8, K * n),
+                                   ("last_values", last_values, torch.float32, n), ("last_dones", u8[1], torch.uint8, n),
+                                   ("advantages", advantages, torch.float32, K * n),
+                                   ("returns", returns, torch.float32, K * n)):
+            if t.dtype != dt or not t.is_contiguous() or t.numel() != numel or t.device != self.device:
+                raise ValueError(f"{name} must be a contiguous {dt} tensor of {numel} elements on {self.device}")
+        st = self.lib.ha_gae(n, K, float(gamma), float(gae_lambda), rewards.data_ptr(), values.data_ptr(),
+                             u8[0].data_ptr(), last_values.data_ptr(), u8[1].data_ptr(), advantages.data_ptr(),
+                             returns.data_ptr(), self._stream())
+        self._check(None, st, "ha_gae")
+        return advantages, returns
+
+    # ------------------------------------------------------------------ host
+    def host_step(self, obs, episode_start, states, seed, step_index, deterministic=False, write_state=True,
+                  env_id_offset=0):
+        """ha_host_policy_step over NumPy: obs [n,13], episode_start [n], states = (h_pi, c_pi, h_vf,
+        c_vf), C-contiguous float32 [n,128] arrays updated IN PLACE (unless write_state=False) ->
+        a dict of every output of STEP_OUTPUTS.  The device kernel's arithmetic on the CPU."""
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        n = obs.shape[0]
+        es = np.ascontiguousarray(np.asarray(episode_start).reshape(-1), dtype=np.uint8)
+        if obs.shape != (n, OBS_DIM) or es.shape != (n,):
+            raise ValueError(f"obs must be [n, {OBS_DIM}] and episode_start [n]")
+        if len(states) != 4:
+            raise ValueError("states is (h_pi, c_pi, h_vf, c_vf)")
+        for name, a in zip(STATE_NAMES, states):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous
+                    and a.shape == (n, HIDDEN)):
+                raise ValueError(f"{name} must be a C-contiguous float32 [{n}, {HIDDEN}] array")
+        res = {name: np.empty((n,) + tail, np.float32) for name, tail in STEP_OUTPUTS}
+        st = self.lib.ha_host_policy_step(ctypes.byref(self._w), n, int(env_id_offset), int(seed) & (2 ** 64 - 1),
+                                          int(step_index), int(bool(deterministic)), int(bool(write_state)),
+                                          obs.ctypes.data, es.ctypes.data, *(a.ctypes.data for a in states),
+                                          *(res[name].ctypes.data for name, _ in STEP_OUTPUTS))
+        self._check(None, st, "ha_host_policy_step")
+        return res
+
+    def host_gae(self, rewards, values, episode_starts, last_values, last_dones, gamma, gae_lambda):
+        """ha_host_gae over [K,N] NumPy arrays -> (advantages, returns)."""
+        rewards = np.ascontiguousarray(rewards, dtype=np.float32)
+        K, n = rewards.shape
+        values = np.ascontiguousarray(values, dtype=np.float32)
+        es = np.ascontiguousarray(episode_starts, dtype=np.uint8)
+        lv = np.ascontiguousarray(last_values, dtype=np.float32)
+        ld = np.ascontiguousarray(last_dones, dtype=np.uint8)
+        if values.shape != (K, n) or es.shape != (K, n) or lv.shape != (n,) or ld.shape != (n,):
+            raise ValueError("rewards, values, episode_starts are [K, N]; last_values, last_dones [N]")
+        adv = np.empty((K, n), np.float32)
+        ret = np.empty((K, n), np.float32)
+        st = self.lib.ha_host_gae(n, K, float(gamma), float(gae_lambda), rewards.ctypes.data, values.ctypes.data,
+                                  es.ctypes.data, lv.ctypes.data, ld.ctypes.data, adv.ctypes.data, ret.ctypes.data)
+        self._check(None, st, "ha_host_gae")
+        return adv, ret
+
+    def close(self):
+        if self._h is not None:
+            import torch
+            torch.cuda.synchronize(self.device)
+            self.lib.ha_policy_destroy(self._h)
+            self._h = None
+        self.h_pi = self.c_pi = self.h_vf = self.c_vf = None
 
     def __del__(self):
         try:

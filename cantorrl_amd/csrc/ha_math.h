@@ -1,5 +1,6 @@
 // ha_math.h -- the scalar arithmetic of the RecurrentPPO actor (include/hedge_actor.h,
-// "Arithmetic contract"), shared by the HIP kernel (__device__) and ha_host_step (__host__):
+// "Arithmetic contract"), its rollout policy (sampling, log-probability) and GAE, shared by the
+// HIP kernels (__device__) and ha_host_step / ha_host_policy_step / ha_host_gae (__host__):
 // one implementation, so the two agree bit for bit.  The library is compiled with
 // -ffp-contract=off; f64 + - * / are IEEE on both sides and he::exp_k is host / device identical.
 #pragma once
@@ -57,6 +58,68 @@ HE_HD float mlp_act(float x, bool relu) { return relu ? (x > 0.0f ? x : (x != x 
 HE_HD float squash_action(float mean, bool tanh_squash) {
     const float a = tanh_squash ? tanhf_r(mean) : mean;
     return he::np_clipf(a, -1.0f, 1.0f);
+}
+
+// ---------------------------------------------------------------- the rollout policy (ha_policy_step)
+// std = f32(exp(f64(log_std)))
+HE_HD float policy_std(float log_std) { return (float)he::exp_k((double)log_std); }
+
+// Contract steps 4-6: the diagonal-Gaussian sample of env g at step_index, its clipped form and
+// its log-probability.  One Philox block per (seed, step_index, g): nothing depends on how the
+// envs are split over calls.
+HE_HD void sample_action(const float* mean, const float* log_std, const float* stdv, uint64_t seed,
+                         uint64_t step_index, uint64_t g, bool deterministic, float* a, float* env_a,
+                         float* log_prob) {
+    float eps[kAct] = {0.0f, 0.0f};
+    if (!deterministic) {
+        he::u32x4 ctr;
+        ctr.x = (uint32_t)step_index;
+        ctr.y = (uint32_t)(step_index >> 32);
+        ctr.z = (uint32_t)g;
+        ctr.w = (uint32_t)(g >> 32);
+        const he::u32x4 r = he::philox4x32_10(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
+        double z0, z1;
+        he::box_muller(he::u01(r.x, r.y), he::u01(r.z, r.w), &z0, &z1);
+        eps[0] = (float)z0;
+        eps[1] = (float)z1;
+    }
+    double lp = 0.0;
+    for (int j = 0; j < kAct; ++j) {
+        a[j] = deterministic ? mean[j] : fmaf(stdv[j], eps[j], mean[j]);
+        env_a[j] = he::np_clipf(a[j], -1.0f, 1.0f);
+        const double z = ((double)a[j] - (double)mean[j]) / (double)stdv[j];
+        const double zz = z * z;
+        const double t = -0.5 * zz;
+        const double u = t - (double)log_std[j];
+        const double v = u - 0.9189385332046727;
+        lp = lp + v;
+    }
+    *log_prob = (float)lp;
+}
+
+// Contract step 7 for env e: SB3's compute_returns_and_advantage in f32, k = K-1 .. 0; every
+// array is [K][n], so a wave of consecutive e reads consecutive addresses.
+HE_HD void gae_env(int64_t e, int64_t n, int64_t K, float g32, float gl32, const float* rewards,
+                   const float* values, const uint8_t* episode_starts, const float* last_values,
+                   const uint8_t* last_dones, float* advantages, float* returns) {
+    float last = 0.0f;
+    float nv = last_values[e];
+    float nnt = 1.0f - (float)last_dones[e];
+    for (int64_t k = K - 1; k >= 0; --k) {
+        const int64_t i = k * n + e;
+        const float v = values[i];
+        const float gv = g32 * nv;
+        const float gvn = gv * nnt;
+        const float rg = rewards[i] + gvn;
+        const float delta = rg - v;
+        const float gn = gl32 * nnt;
+        const float gl = gn * last;
+        last = delta + gl;
+        advantages[i] = last;
+        returns[i] = last + v;
+        nv = v;
+        nnt = 1.0f - (float)episode_starts[i];
+    }
 }
 
 }  // namespace ha

@@ -19,6 +19,12 @@
 //   MLP     waves 0, 1 each own 32 of the 64 outputs of a layer (one accumulator, K = 128 then
 //           64), activations through LDS; the 2 x 64 action head is a VALU fmaf chain.
 // 512 x 142 x 4 B of packed gate weights are read per tile from L2.
+//
+// policy_step_kernel (ha_policy_step) is the same tile body (net_tile) over a grid of (tiles, 2):
+// blockIdx.y = 0 runs the actor's packed tensors on h_pi / c_pi and ends in the sampling and the
+// log-probability, blockIdx.y = 1 runs the critic's on h_vf / c_vf and ends in the value.  Both
+// stage the same obs; registers and LDS stay at actor_kernel's figures.  gae_kernel (ha_gae) is
+// one thread per env over [K][n] arrays.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -40,6 +46,18 @@ constexpr int kThreads = 256;             // 4 waves: one per 32 hidden units
 constexpr int kStepsG = kKp / 2;          // 71 k-steps of the gate product
 constexpr int kLd = kTile + 1;            // LDS row stride (floats): staging writes run down a column
 
+// one network (LSTM + two Linear + head) packed in the kernel's fragment order
+struct Net {
+    const float4* wg;     // [4][71][64] {i, f, g, o}
+    const float* bg;      // [512] b_ih + b_hh
+    const float* w1p;     // [2][64][64]
+    const float* b1;
+    const float* w2p;     // [2][32][64]
+    const float* b2;
+    const float* w3;      // [2][64] (the critic: [1][64])
+    const float* b3;
+};
+
 struct Params {
     int64_t n;
     const float* obs;
@@ -49,17 +67,40 @@ struct Params {
     float* actions;
     float* mean_out;
     float* obs_norm_out;
-    const float4* wg;     // [4][71][64] {i, f, g, o}
-    const float* bg;      // [512] b_ih + b_hh
-    const float* w1p;     // [2][64][64]
-    const float* b1;
-    const float* w2p;     // [2][32][64]
-    const float* b2;
-    const float* w3;      // [2][64]
-    const float* b3;
+    Net net;
     const double* stats;  // [3][13] mean, sd, RN(1 / sd); NULL = no normalisation
     double clip;
     int32_t has_clip, relu, tanh_squash;
+};
+
+struct PolicyParams {
+    int64_t n, goff;
+    uint64_t seed, step_index;
+    const float* obs;
+    const uint8_t* start;
+    float* h_pi;
+    float* c_pi;
+    float* h_vf;
+    float* c_vf;
+    float* actions;
+    float* env_actions;
+    float* values;
+    float* log_probs;
+    float* mean_out;
+    float* obs_norm_out;
+    Net pi, vf;
+    const float* ls;      // [4] log_std[2], std[2]
+    const double* stats;
+    double clip;
+    int32_t has_clip, relu, deterministic, write_state;
+};
+
+// the tile's LDS: 52,536 B
+struct Tile {
+    float xh[kKp][kLd];
+    float hn[kHid][kLd];
+    float a1[kMlp][kLd];
+    float a2[kMlp][kLd];
 };
 
 // C/D row of accumulator register r in lane-half hi (32x32 tile): (r & 3) + 8 (r >> 2) + 4 hi
@@ -83,34 +124,33 @@ __device__ __forceinline__ void mlp_slice(const float* __restrict__ wp, const fl
     for (int r = 0; r < 16; ++r) out[rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi][col] = mlp_act(a[r], relu);
 }
 
-__global__ __launch_bounds__(kThreads, 2) void actor_kernel(const Params p) {
-    __shared__ float xh[kKp][kLd];
-    __shared__ float hn[kHid][kLd];
-    __shared__ float a1[kMlp][kLd];
-    __shared__ float a2[kMlp][kLd];
+// The tile body: stage, gates, cell update (h, c stored when write_state), the two MLP layers.
+// On return (after a barrier) t.a2[k][env] holds the last hidden layer of the tile's envs.
+__device__ __forceinline__ void net_tile(Tile& t, const Net& net, int64_t n, int64_t e0, const float* __restrict__ obs,
+                                         const uint8_t* __restrict__ start, float* h, float* c, bool write_state,
+                                         float* obs_norm_out, const double* __restrict__ stats, bool has_clip,
+                                         double clip, bool relu) {
     const int tid = threadIdx.x;
-    const int64_t e0 = (int64_t)blockIdx.x * kTile;
-
     // ---- stage [x | h | 0]; envs past n are zero columns
     for (int idx = tid; idx < kTile * kObs; idx += kThreads) {
         const int el = idx / kObs, k = idx - el * kObs;
         const int64_t e = e0 + el;
         float v = 0.0f;
-        if (e < p.n) {
-            v = p.obs[e * kObs + k];
-            if (p.stats) v = norm_obs(v, p.stats[k], p.stats[kObs + k], p.stats[2 * kObs + k], p.has_clip != 0, p.clip);
-            if (p.obs_norm_out) p.obs_norm_out[e * kObs + k] = v;
+        if (e < n) {
+            v = obs[e * kObs + k];
+            if (stats) v = norm_obs(v, stats[k], stats[kObs + k], stats[2 * kObs + k], has_clip, clip);
+            if (obs_norm_out) obs_norm_out[e * kObs + k] = v;
         }
-        xh[k][el] = v;
+        t.xh[k][el] = v;
     }
     for (int idx = tid; idx < kTile * kHid; idx += kThreads) {
         const int el = idx >> 7, u = idx & (kHid - 1);
         const int64_t e = e0 + el;
         float v = 0.0f;
-        if (e < p.n && !p.start[e]) v = p.h[e * kHid + u];
-        xh[kObs + u][el] = v;
+        if (e < n && !start[e]) v = h[e * kHid + u];
+        t.xh[kObs + u][el] = v;
     }
-    if (tid < kTile) xh[kKx][tid] = 0.0f;
+    if (tid < kTile) t.xh[kKx][tid] = 0.0f;
     __syncthreads();
 
     // ---- gates: wave = unit group, four accumulators
@@ -122,14 +162,14 @@ __global__ __launch_bounds__(kThreads, 2) void actor_kernel(const Params p) {
         for (int g = 0; g < 4; ++g)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float4 b = *(const float4*)(p.bg + g * kHid + wave * 32 + 8 * q + 4 * hi);
+                const float4 b = *(const float4*)(net.bg + g * kHid + wave * 32 + 8 * q + 4 * hi);
                 acc[g][4 * q + 0] = b.x; acc[g][4 * q + 1] = b.y; acc[g][4 * q + 2] = b.z; acc[g][4 * q + 3] = b.w;
             }
-        const float4* wp = p.wg + (size_t)wave * kStepsG * 64 + lane;
+        const float4* wp = net.wg + (size_t)wave * kStepsG * 64 + lane;
 #pragma unroll 4
         for (int s = 0; s < kStepsG; ++s) {
             const float4 w = wp[s * 64];
-            const float b = xh[2 * s + hi][col];
+            const float b = t.xh[2 * s + hi][col];
             acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, b, acc[0], 0, 0, 0);
             acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, b, acc[1], 0, 0, 0);
             acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, b, acc[2], 0, 0, 0);
@@ -137,44 +177,100 @@ __global__ __launch_bounds__(kThreads, 2) void actor_kernel(const Params p) {
         }
         // ---- cell update in registers
         const int64_t e = e0 + col;
-        const bool valid = e < p.n;
-        const bool fresh = valid && p.start[e] != 0;
+        const bool valid = e < n;
+        const bool fresh = valid && start[e] != 0;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int u = wave * 32 + 8 * q + 4 * hi;
             float4 cv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (valid && !fresh) cv = *(const float4*)(p.c + e * kHid + u);
+            if (valid && !fresh) cv = *(const float4*)(c + e * kHid + u);
             float cc[4] = {cv.x, cv.y, cv.z, cv.w};
             float hv[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int r = 4 * q + j;
                 hv[j] = cell_update(acc[0][r], acc[1][r], acc[2][r], acc[3][r], &cc[j]);
-                hn[u + j][col] = hv[j];
+                t.hn[u + j][col] = hv[j];
             }
-            if (valid) {
-                *(float4*)(p.c + e * kHid + u) = make_float4(cc[0], cc[1], cc[2], cc[3]);
-                *(float4*)(p.h + e * kHid + u) = make_float4(hv[0], hv[1], hv[2], hv[3]);
+            if (valid && write_state) {
+                *(float4*)(c + e * kHid + u) = make_float4(cc[0], cc[1], cc[2], cc[3]);
+                *(float4*)(h + e * kHid + u) = make_float4(hv[0], hv[1], hv[2], hv[3]);
             }
         }
     }
     __syncthreads();
 
-    // ---- MLP and the action head
-    if (wave < 2) mlp_slice<kHid>(p.w1p, p.b1, hn, a1, wave, lane, p.relu != 0);
+    // ---- MLP
+    if (wave < 2) mlp_slice<kHid>(net.w1p, net.b1, t.hn, t.a1, wave, lane, relu);
     __syncthreads();
-    if (wave < 2) mlp_slice<kMlp>(p.w2p, p.b2, a1, a2, wave, lane, p.relu != 0);
+    if (wave < 2) mlp_slice<kMlp>(net.w2p, net.b2, t.a1, t.a2, wave, lane, relu);
     __syncthreads();
+}
+
+// one output of the head for env column el: chain(b; w a2)
+__device__ __forceinline__ float head_chain(const float* __restrict__ w, float b, const float (*a2)[kLd], int el) {
+    float m = b;
+    for (int k = 0; k < kMlp; ++k) m = fmaf(w[k], a2[k][el], m);
+    return m;
+}
+
+__global__ __launch_bounds__(kThreads, 2) void actor_kernel(const Params p) {
+    __shared__ Tile t;
+    const int tid = threadIdx.x;
+    const int64_t e0 = (int64_t)blockIdx.x * kTile;
+    net_tile(t, p.net, p.n, e0, p.obs, p.start, p.h, p.c, true, p.obs_norm_out, p.stats, p.has_clip != 0, p.clip,
+             p.relu != 0);
     if (tid < kTile * kAct) {
         const int el = tid >> 1, j = tid & 1;
         const int64_t e = e0 + el;
-        float m = p.b3[j];
-        for (int k = 0; k < kMlp; ++k) m = fmaf(p.w3[j * kMlp + k], a2[k][el], m);
+        const float m = head_chain(p.net.w3 + j * kMlp, p.net.b3[j], t.a2, el);
         if (e < p.n) {
             if (p.mean_out) p.mean_out[e * kAct + j] = m;
             p.actions[e * kAct + j] = squash_action(m, p.tanh_squash != 0);
         }
     }
+}
+
+// grid (tiles, 2): y = 0 the actor and the sampling, y = 1 the critic and the value
+__global__ __launch_bounds__(kThreads, 2) void policy_step_kernel(const PolicyParams p) {
+    __shared__ Tile t;
+    const int tid = threadIdx.x;
+    const int64_t e0 = (int64_t)blockIdx.x * kTile;
+    const bool critic = blockIdx.y != 0;
+    const Net net = critic ? p.vf : p.pi;
+    net_tile(t, net, p.n, e0, p.obs, p.start, critic ? p.h_vf : p.h_pi, critic ? p.c_vf : p.c_pi, p.write_state != 0,
+             critic ? nullptr : p.obs_norm_out, p.stats, p.has_clip != 0, p.clip, p.relu != 0);
+    if (tid >= kTile * kAct) return;   // wave 0: lane pair (2 el, 2 el + 1) = the two head outputs of env el
+    const int el = tid >> 1, j = tid & 1;
+    const int64_t e = e0 + el;
+    if (critic) {
+        if (j == 0) {
+            const float v = head_chain(net.w3, net.b3[0], t.a2, el);
+            if (e < p.n) p.values[e] = v;
+        }
+        return;
+    }
+    const float m = head_chain(net.w3 + j * kMlp, net.b3[j], t.a2, el);
+    const float mo = __shfl_xor(m, 1);
+    const float mean[kAct] = {j ? mo : m, j ? m : mo};
+    if (j != 0 || e >= p.n) return;
+    float a[kAct], ea[kAct], lp;
+    sample_action(mean, p.ls, p.ls + kAct, p.seed, p.step_index, (uint64_t)(p.goff + e), p.deterministic != 0, a, ea,
+                  &lp);
+    *(float2*)(p.actions + e * kAct) = make_float2(a[0], a[1]);
+    *(float2*)(p.env_actions + e * kAct) = make_float2(ea[0], ea[1]);
+    p.log_probs[e] = lp;
+    if (p.mean_out) *(float2*)(p.mean_out + e * kAct) = make_float2(mean[0], mean[1]);
+}
+
+__global__ __launch_bounds__(256) void gae_kernel(int64_t n, int64_t K, float g32, float gl32,
+                                                  const float* __restrict__ rewards, const float* __restrict__ values,
+                                                  const uint8_t* __restrict__ episode_starts,
+                                                  const float* __restrict__ last_values,
+                                                  const uint8_t* __restrict__ last_dones, float* __restrict__ advantages,
+                                                  float* __restrict__ returns) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n) gae_env(e, n, K, g32, gl32, rewards, values, episode_starts, last_values, last_dones, advantages, returns);
 }
 
 struct AccIn {
@@ -228,11 +324,36 @@ struct ha_actor {
     Params p;     // the constant part of the kernel's arguments
 };
 
+struct ha_policy {
+    char err[256];
+    void* blob;       // both packed networks, log_std / std, the statistics
+    PolicyParams p;
+};
+
 namespace {
 
-ha_status fail(ha_actor* a, ha_status st, const char* msg) {
-    snprintf(a ? a->err : g_err, 256, "%s", msg);
+ha_status fail_to(char* err, ha_status st, const char* msg) {
+    snprintf(err ? err : g_err, 256, "%s", msg);
     return st;
+}
+ha_status fail(ha_actor* a, ha_status st, const char* msg) { return fail_to(a ? a->err : nullptr, st, msg); }
+ha_status fail(ha_policy* a, ha_status st, const char* msg) { return fail_to(a ? a->err : nullptr, st, msg); }
+
+// one network's HOST tensors, torch layout; w3 is [n_out][64]
+struct HostNet {
+    const float *w_ih, *w_hh, *b_ih, *b_hh, *w1, *b1, *w2, *b2, *w3, *b3;
+    int n_out;
+    bool complete() const { return w_ih && w_hh && b_ih && b_hh && w1 && b1 && w2 && b2 && w3 && b3; }
+};
+
+HostNet actor_net(const ha_weights* w) {
+    return {w->w_ih, w->w_hh, w->b_ih, w->b_hh, w->w1, w->b1, w->w2, w->b2, w->w3, w->b3, kAct};
+}
+HostNet actor_net(const ha_policy_weights* w) {
+    return {w->w_ih, w->w_hh, w->b_ih, w->b_hh, w->w1, w->b1, w->w2, w->b2, w->w3, w->b3, kAct};
+}
+HostNet critic_net(const ha_policy_weights* w) {
+    return {w->c_w_ih, w->c_w_hh, w->c_b_ih, w->c_b_hh, w->v1, w->vb1, w->v2, w->vb2, w->v3, w->vb3, 1};
 }
 
 ha_status check_weights(const ha_weights* w, ha_actor* a) {
@@ -250,16 +371,166 @@ ha_status check_weights(const ha_weights* w, ha_actor* a) {
     }
     if (w->activation != HA_ACT_TANH && w->activation != HA_ACT_RELU) return fail(a, HE_EINVAL, "unknown activation");
     if (w->squash != HA_SQUASH_CLIP && w->squash != HA_SQUASH_TANH) return fail(a, HE_EINVAL, "unknown squash");
-    if (!w->w_ih || !w->w_hh || !w->b_ih || !w->b_hh || !w->w1 || !w->b1 || !w->w2 || !w->b2 || !w->w3 || !w->b3)
-        return fail(a, HE_EINVAL, "an actor tensor is NULL");
+    if (!actor_net(w).complete()) return fail(a, HE_EINVAL, "an actor tensor is NULL");
+    if ((w->obs_mean == nullptr) != (w->obs_var == nullptr))
+        return fail(a, HE_EINVAL, "obs_mean and obs_var come together");
+    return HE_OK;
+}
+
+ha_status check_policy_weights(const ha_policy_weights* w, ha_policy* a) {
+    if (!w) return fail(a, HE_EINVAL, "weights is NULL");
+    if (w->abi_version != HA_POLICY_ABI_VERSION) return fail(a, HE_EINVAL, "ha_policy_weights.abi_version mismatch");
+    char m[200];
+    if (w->n_lstm_layers != 1) {
+        snprintf(m, sizeof m, "n_lstm_layers = %d: actor and critic have one LSTM layer each", w->n_lstm_layers);
+        return fail(a, HE_ESHAPE, m);
+    }
+    if (w->obs_dim != kObs || w->hidden != kHid || w->mlp_width != kMlp || w->act_dim != kAct) {
+        snprintf(m, sizeof m,
+                 "policy shape obs %d / lstm %d / mlp %d / action %d: only 13 / 128 / 64-64 / 2 actions / 1 value is built",
+                 w->obs_dim, w->hidden, w->mlp_width, w->act_dim);
+        return fail(a, HE_ESHAPE, m);
+    }
+    if (w->activation != HA_ACT_TANH && w->activation != HA_ACT_RELU) return fail(a, HE_EINVAL, "unknown activation");
+    if (!actor_net(w).complete() || !w->log_std) return fail(a, HE_EINVAL, "an actor tensor (or log_std) is NULL");
+    if (!critic_net(w).complete()) return fail(a, HE_EINVAL, "a critic tensor is NULL");
     if ((w->obs_mean == nullptr) != (w->obs_var == nullptr))
         return fail(a, HE_EINVAL, "obs_mean and obs_var come together");
     return HE_OK;
 }
 
 // W[j][k] of the gate product over [x | h | 0]
-inline float gate_w(const ha_weights* w, int j, int k) {
-    return k < kObs ? w->w_ih[j * kObs + k] : (k < kKx ? w->w_hh[j * kHid + (k - kObs)] : 0.0f);
+inline float gate_w(const HostNet& w, int j, int k) {
+    return k < kObs ? w.w_ih[j * kObs + k] : (k < kKx ? w.w_hh[j * kHid + (k - kObs)] : 0.0f);
+}
+
+// one packed network: float4-aligned sections, in floats
+constexpr size_t o_wg = 0, n_wg = (size_t)4 * kStepsG * 64 * 4;
+constexpr size_t o_bg = o_wg + n_wg, o_w1 = o_bg + kGates, o_b1 = o_w1 + (size_t)kMlp * kHid;
+constexpr size_t o_w2 = o_b1 + kMlp, o_b2 = o_w2 + (size_t)kMlp * kMlp, o_w3 = o_b2 + kMlp;
+constexpr size_t o_b3 = o_w3 + kAct * kMlp, kNetFloats = o_b3 + 4;
+constexpr size_t kStatFloats = 2 * 3 * kObs;   // [3][13] doubles
+static_assert(kNetFloats % 4 == 0, "the next section stays 16-byte aligned");
+
+void pack_net(const HostNet& w, float* dst) {
+    for (int ug = 0; ug < 4; ++ug)
+        for (int s = 0; s < kStepsG; ++s)
+            for (int l = 0; l < 64; ++l)
+                for (int g = 0; g < 4; ++g)
+                    dst[o_wg + (((size_t)ug * kStepsG + s) * 64 + l) * 4 + g] =
+                        gate_w(w, g * kHid + ug * 32 + (l & 31), 2 * s + (l >> 5));
+    for (int j = 0; j < kGates; ++j) dst[o_bg + j] = w.b_ih[j] + w.b_hh[j];
+    for (int rt = 0; rt < 2; ++rt)
+        for (int l = 0; l < 64; ++l) {
+            for (int s = 0; s < kHid / 2; ++s)
+                dst[o_w1 + ((size_t)rt * (kHid / 2) + s) * 64 + l] = w.w1[(rt * 32 + (l & 31)) * kHid + 2 * s + (l >> 5)];
+            for (int s = 0; s < kMlp / 2; ++s)
+                dst[o_w2 + ((size_t)rt * (kMlp / 2) + s) * 64 + l] = w.w2[(rt * 32 + (l & 31)) * kMlp + 2 * s + (l >> 5)];
+        }
+    memcpy(dst + o_b1, w.b1, kMlp * sizeof(float));
+    memcpy(dst + o_b2, w.b2, kMlp * sizeof(float));
+    memcpy(dst + o_w3, w.w3, (size_t)w.n_out * kMlp * sizeof(float));
+    memcpy(dst + o_b3, w.b3, w.n_out * sizeof(float));
+}
+
+Net net_at(const float* d) {
+    Net n;
+    n.wg = (const float4*)(d + o_wg);
+    n.bg = d + o_bg;
+    n.w1p = d + o_w1;
+    n.b1 = d + o_b1;
+    n.w2p = d + o_w2;
+    n.b2 = d + o_b2;
+    n.w3 = d + o_w3;
+    n.b3 = d + o_b3;
+    return n;
+}
+
+// [3][13] mean, sd = sqrt(var + eps), RN(1 / sd) at an 8-byte aligned dst
+void pack_stats(const double* mean, const double* var, double epsilon, float* dst) {
+    double stt[3 * kObs];
+    for (int k = 0; k < kObs; ++k) {
+        stt[k] = mean[k];
+        stt[kObs + k] = sqrt(var[k] + epsilon);
+        stt[2 * kObs + k] = 1.0 / stt[kObs + k];
+    }
+    memcpy(dst, stt, sizeof stt);
+}
+
+// Contract steps 1, 3-5 for one env on the host: x is the (normalised) obs; h, c are read unless
+// fresh and written when write_state; a2 receives the last hidden layer.
+void host_net_env(const HostNet& w, const float* x, bool fresh, float* h, float* c, bool write_state, bool relu,
+                  float* a2) {
+    float xh[kKp], hn[kHid], cn[kHid], a1[kMlp];
+    for (int k = 0; k < kObs; ++k) xh[k] = x[k];
+    for (int u = 0; u < kHid; ++u) xh[kObs + u] = fresh ? 0.0f : h[u];
+    xh[kKx] = 0.0f;
+    for (int u = 0; u < kHid; ++u) {
+        float pre[4];
+        for (int g = 0; g < 4; ++g) {
+            const int j = g * kHid + u;
+            float acc = w.b_ih[j] + w.b_hh[j];
+            for (int k = 0; k < kKp; ++k) acc = fmaf(gate_w(w, j, k), xh[k], acc);
+            pre[g] = acc;
+        }
+        float cv = fresh ? 0.0f : c[u];
+        hn[u] = cell_update(pre[0], pre[1], pre[2], pre[3], &cv);
+        cn[u] = cv;
+    }
+    if (write_state) {
+        memcpy(h, hn, sizeof hn);
+        memcpy(c, cn, sizeof cn);
+    }
+    for (int j = 0; j < kMlp; ++j) {
+        float acc = w.b1[j];
+        for (int k = 0; k < kHid; ++k) acc = fmaf(w.w1[j * kHid + k], hn[k], acc);
+        a1[j] = mlp_act(acc, relu);
+    }
+    for (int j = 0; j < kMlp; ++j) {
+        float acc = w.b2[j];
+        for (int k = 0; k < kMlp; ++k) acc = fmaf(w.w2[j * kMlp + k], a1[k], acc);
+        a2[j] = mlp_act(acc, relu);
+    }
+}
+
+inline float host_head(const HostNet& w, int j, const float* a2) {
+    float m = w.b3[j];
+    for (int k = 0; k < kMlp; ++k) m = fmaf(w.w3[j * kMlp + k], a2[k], m);
+    return m;
+}
+
+// the blob of a policy: [actor | critic | log_std, std | statistics]
+constexpr size_t o_ls = 2 * kNetFloats, o_pst = o_ls + 4, kPolicyFloats = o_pst + kStatFloats;
+
+void pack_policy(const ha_policy_weights* w, float* dst) {
+    pack_net(actor_net(w), dst);
+    pack_net(critic_net(w), dst + kNetFloats);
+    for (int j = 0; j < kAct; ++j) {
+        dst[o_ls + j] = w->log_std[j];
+        dst[o_ls + kAct + j] = policy_std(w->log_std[j]);
+    }
+    if (w->obs_mean) pack_stats(w->obs_mean, w->obs_var, w->epsilon, dst + o_pst);
+}
+
+void policy_params(const ha_policy_weights* w, const float* d, PolicyParams* p) {
+    memset(p, 0, sizeof *p);
+    p->pi = net_at(d);
+    p->vf = net_at(d + kNetFloats);
+    p->ls = d + o_ls;
+    p->stats = w->obs_mean ? (const double*)(d + o_pst) : nullptr;
+    p->clip = w->clip_obs;
+    p->has_clip = w->has_clip;
+    p->relu = w->activation == HA_ACT_RELU;
+}
+
+ha_status check_gae(int64_t n, int64_t K, double gamma, double gae_lambda, const void* rewards, const void* values,
+                    const void* episode_starts, const void* last_values, const void* last_dones,
+                    const void* advantages, const void* returns) {
+    if (n < 1 || K < 1) return fail_to(nullptr, HE_EINVAL, "n and K must be >= 1");
+    if (!(gamma == gamma) || !(gae_lambda == gae_lambda)) return fail_to(nullptr, HE_EINVAL, "gamma / gae_lambda is NaN");
+    if (!rewards || !values || !episode_starts || !last_values || !last_dones || !advantages || !returns)
+        return fail_to(nullptr, HE_EINVAL, "a GAE buffer is NULL");
+    return HE_OK;
 }
 
 }  // namespace
@@ -270,70 +541,36 @@ const char* ha_version(void) { return "libhedgeactor 1 (gfx950, v_mfma_f32_32x32
 
 const char* ha_last_error(const ha_actor* actor) { return actor ? actor->err : g_err; }
 
+const char* ha_policy_last_error(const ha_policy* policy) { return policy ? policy->err : g_err; }
+
 ha_status ha_create(const ha_weights* w, ha_actor** out) {
-    if (!out) return fail(nullptr, HE_EINVAL, "out is NULL");
+    if (!out) return fail((ha_actor*)nullptr, HE_EINVAL, "out is NULL");
     *out = nullptr;
     ha_status st = check_weights(w, nullptr);
     if (st != HE_OK) return st;
-    // the blob: float4-aligned sections, in floats
-    const size_t o_wg = 0, n_wg = (size_t)4 * kStepsG * 64 * 4;
-    const size_t o_bg = o_wg + n_wg, o_w1 = o_bg + kGates, o_b1 = o_w1 + (size_t)kMlp * kHid;
-    const size_t o_w2 = o_b1 + kMlp, o_b2 = o_w2 + (size_t)kMlp * kMlp, o_w3 = o_b2 + kMlp;
-    const size_t o_b3 = o_w3 + kAct * kMlp, o_st = o_b3 + 4;   // stats: doubles, 8-byte aligned (o_st even)
-    const size_t total = o_st + 2 * 3 * kObs;
+    const size_t o_st = kNetFloats;   // stats: doubles, 8-byte aligned (o_st even)
+    const size_t total = o_st + kStatFloats;
     std::vector<float> hbuf(total, 0.0f);
-    for (int ug = 0; ug < 4; ++ug)
-        for (int s = 0; s < kStepsG; ++s)
-            for (int l = 0; l < 64; ++l)
-                for (int g = 0; g < 4; ++g)
-                    hbuf[o_wg + (((size_t)ug * kStepsG + s) * 64 + l) * 4 + g] =
-                        gate_w(w, g * kHid + ug * 32 + (l & 31), 2 * s + (l >> 5));
-    for (int j = 0; j < kGates; ++j) hbuf[o_bg + j] = w->b_ih[j] + w->b_hh[j];
-    for (int rt = 0; rt < 2; ++rt)
-        for (int l = 0; l < 64; ++l) {
-            for (int s = 0; s < kHid / 2; ++s)
-                hbuf[o_w1 + ((size_t)rt * (kHid / 2) + s) * 64 + l] = w->w1[(rt * 32 + (l & 31)) * kHid + 2 * s + (l >> 5)];
-            for (int s = 0; s < kMlp / 2; ++s)
-                hbuf[o_w2 + ((size_t)rt * (kMlp / 2) + s) * 64 + l] = w->w2[(rt * 32 + (l & 31)) * kMlp + 2 * s + (l >> 5)];
-        }
-    memcpy(&hbuf[o_b1], w->b1, kMlp * sizeof(float));
-    memcpy(&hbuf[o_b2], w->b2, kMlp * sizeof(float));
-    memcpy(&hbuf[o_w3], w->w3, kAct * kMlp * sizeof(float));
-    memcpy(&hbuf[o_b3], w->b3, kAct * sizeof(float));
-    if (w->obs_mean) {
-        double stt[3 * kObs];
-        for (int k = 0; k < kObs; ++k) {
-            stt[k] = w->obs_mean[k];
-            stt[kObs + k] = sqrt(w->obs_var[k] + w->epsilon);
-            stt[2 * kObs + k] = 1.0 / stt[kObs + k];
-        }
-        memcpy(&hbuf[o_st], stt, sizeof stt);
-    }
+    pack_net(actor_net(w), hbuf.data());
+    if (w->obs_mean) pack_stats(w->obs_mean, w->obs_var, w->epsilon, &hbuf[o_st]);
     ha_actor* a = new (std::nothrow) ha_actor();
-    if (!a) return fail(nullptr, HE_ENOMEM, "host allocation failed");
+    if (!a) return fail((ha_actor*)nullptr, HE_ENOMEM, "host allocation failed");
     a->err[0] = 0;
     a->blob = nullptr;
     if (hipMalloc(&a->blob, total * sizeof(float)) != hipSuccess) {
         delete a;
         (void)hipGetLastError();
-        return fail(nullptr, HE_ENOMEM, "hipMalloc of the packed weights failed (no HIP device?)");
+        return fail((ha_actor*)nullptr, HE_ENOMEM, "hipMalloc of the packed weights failed (no HIP device?)");
     }
     if (hipMemcpy(a->blob, hbuf.data(), total * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipFree(a->blob);
         delete a;
-        return fail(nullptr, HE_EHIP, "upload of the packed weights failed");
+        return fail((ha_actor*)nullptr, HE_EHIP, "upload of the packed weights failed");
     }
     const float* d = (const float*)a->blob;
     Params& p = a->p;
     memset(&p, 0, sizeof p);
-    p.wg = (const float4*)(d + o_wg);
-    p.bg = d + o_bg;
-    p.w1p = d + o_w1;
-    p.b1 = d + o_b1;
-    p.w2p = d + o_w2;
-    p.b2 = d + o_b2;
-    p.w3 = d + o_w3;
-    p.b3 = d + o_b3;
+    p.net = net_at(d);
     p.stats = w->obs_mean ? (const double*)(d + o_st) : nullptr;
     p.clip = w->clip_obs;
     p.has_clip = w->has_clip;
@@ -396,7 +633,8 @@ ha_status ha_host_step(const ha_weights* w, int64_t n, const float* obs, const u
                        float* c, float* actions, float* mean_out, float* obs_norm_out) {
     ha_status st = check_weights(w, nullptr);
     if (st != HE_OK) return st;
-    if (n < 1 || !obs || !episode_start || !h || !c || !actions) return fail(nullptr, HE_EINVAL, "bad argument");
+    if (n < 1 || !obs || !episode_start || !h || !c || !actions)
+        return fail((ha_actor*)nullptr, HE_EINVAL, "bad argument");
     double sd[kObs], y[kObs];
     if (w->obs_mean)
         for (int k = 0; k < kObs; ++k) {
@@ -404,43 +642,18 @@ ha_status ha_host_step(const ha_weights* w, int64_t n, const float* obs, const u
             y[k] = 1.0 / sd[k];
         }
     const bool relu = w->activation == HA_ACT_RELU, tsq = w->squash == HA_SQUASH_TANH;
+    const HostNet net = actor_net(w);
     for (int64_t e = 0; e < n; ++e) {
-        float xh[kKp], hn[kHid], a1[kMlp], a2[kMlp];
+        float x[kObs], a2[kMlp];
         for (int k = 0; k < kObs; ++k) {
             float v = obs[e * kObs + k];
             if (w->obs_mean) v = norm_obs(v, w->obs_mean[k], sd[k], y[k], w->has_clip != 0, w->clip_obs);
             if (obs_norm_out) obs_norm_out[e * kObs + k] = v;
-            xh[k] = v;
+            x[k] = v;
         }
-        const bool fresh = episode_start[e] != 0;
-        for (int u = 0; u < kHid; ++u) xh[kObs + u] = fresh ? 0.0f : h[e * kHid + u];
-        xh[kKx] = 0.0f;
-        for (int u = 0; u < kHid; ++u) {
-            float pre[4];
-            for (int g = 0; g < 4; ++g) {
-                const int j = g * kHid + u;
-                float acc = w->b_ih[j] + w->b_hh[j];
-                for (int k = 0; k < kKp; ++k) acc = fmaf(gate_w(w, j, k), xh[k], acc);
-                pre[g] = acc;
-            }
-            float cv = fresh ? 0.0f : c[e * kHid + u];
-            hn[u] = cell_update(pre[0], pre[1], pre[2], pre[3], &cv);
-            c[e * kHid + u] = cv;
-        }
-        for (int u = 0; u < kHid; ++u) h[e * kHid + u] = hn[u];
-        for (int j = 0; j < kMlp; ++j) {
-            float acc = w->b1[j];
-            for (int k = 0; k < kHid; ++k) acc = fmaf(w->w1[j * kHid + k], hn[k], acc);
-            a1[j] = mlp_act(acc, relu);
-        }
-        for (int j = 0; j < kMlp; ++j) {
-            float acc = w->b2[j];
-            for (int k = 0; k < kMlp; ++k) acc = fmaf(w->w2[j * kMlp + k], a1[k], acc);
-            a2[j] = mlp_act(acc, relu);
-        }
+        host_net_env(net, x, episode_start[e] != 0, h + e * kHid, c + e * kHid, true, relu, a2);
         for (int j = 0; j < kAct; ++j) {
-            float m = w->b3[j];
-            for (int k = 0; k < kMlp; ++k) m = fmaf(w->w3[j * kMlp + k], a2[k], m);
+            const float m = host_head(net, j, a2);
             if (mean_out) mean_out[e * kAct + j] = m;
             actions[e * kAct + j] = squash_action(m, tsq);
         }
@@ -448,4 +661,158 @@ ha_status ha_host_step(const ha_weights* w, int64_t n, const float* obs, const u
     return HE_OK;
 }
 
+ha_status ha_policy_create(const ha_policy_weights* w, ha_policy** out) {
+    if (!out) return fail((ha_policy*)nullptr, HE_EINVAL, "out is NULL");
+    *out = nullptr;
+    ha_status st = check_policy_weights(w, nullptr);
+    if (st != HE_OK) return st;
+    std::vector<float> hbuf(kPolicyFloats, 0.0f);
+    pack_policy(w, hbuf.data());
+    ha_policy* a = new (std::nothrow) ha_policy();
+    if (!a) return fail((ha_policy*)nullptr, HE_ENOMEM, "host allocation failed");
+    a->err[0] = 0;
+    a->blob = nullptr;
+    if (hipMalloc(&a->blob, kPolicyFloats * sizeof(float)) != hipSuccess) {
+        delete a;
+        (void)hipGetLastError();
+        return fail((ha_policy*)nullptr, HE_ENOMEM, "hipMalloc of the packed weights failed (no HIP device?)");
+    }
+    if (hipMemcpy(a->blob, hbuf.data(), kPolicyFloats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(a->blob);
+        delete a;
+        return fail((ha_policy*)nullptr, HE_EHIP, "upload of the packed weights failed");
+    }
+    policy_params(w, (const float*)a->blob, &a->p);
+    *out = a;
+    return HE_OK;
+}
+
+ha_status ha_policy_destroy(ha_policy* policy) {
+    if (!policy) return HE_EINVAL;
+    if (policy->blob) (void)hipFree(policy->blob);
+    delete policy;
+    return HE_OK;
+}
+
+ha_status ha_policy_update(ha_policy* policy, const ha_policy_weights* w) {
+    if (!policy) return HE_EINVAL;
+    ha_status st = check_policy_weights(w, policy);
+    if (st != HE_OK) return st;
+    std::vector<float> hbuf(kPolicyFloats, 0.0f);
+    pack_policy(w, hbuf.data());
+    // steps already enqueued read the old tensors to their end
+    if (hipDeviceSynchronize() != hipSuccess) return fail(policy, HE_EHIP, "hipDeviceSynchronize failed");
+    if (hipMemcpy(policy->blob, hbuf.data(), kPolicyFloats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(policy, HE_EHIP, "upload of the packed weights failed");
+    policy_params(w, (const float*)policy->blob, &policy->p);
+    return HE_OK;
+}
+
+ha_status ha_policy_step(ha_policy* policy, int64_t n, int64_t env_id_offset, uint64_t seed, uint64_t step_index,
+                         int32_t deterministic, int32_t write_state, const float* obs, const uint8_t* episode_start,
+                         float* h_pi, float* c_pi, float* h_vf, float* c_vf, float* actions, float* env_actions,
+                         float* values, float* log_probs, float* mean_out, float* obs_norm_out, void* stream) {
+    if (!policy) return HE_EINVAL;
+    if (n < 1 || n > ((int64_t)1 << 30)) return fail(policy, HE_EINVAL, "n must be in [1, 2^30]");
+    if (env_id_offset < 0) return fail(policy, HE_EINVAL, "env_id_offset must be >= 0");
+    if (!obs || !episode_start || !h_pi || !c_pi || !h_vf || !c_vf || !actions || !env_actions || !values || !log_probs)
+        return fail(policy, HE_EINVAL, "a required buffer is NULL");
+    if ((((uintptr_t)h_pi) | ((uintptr_t)c_pi) | ((uintptr_t)h_vf) | ((uintptr_t)c_vf)) & 15u)
+        return fail(policy, HE_EINVAL, "the LSTM states must be 16-byte aligned");
+    if ((((uintptr_t)actions) | ((uintptr_t)env_actions) | ((uintptr_t)mean_out)) & 7u)
+        return fail(policy, HE_EINVAL, "actions, env_actions and mean_out must be 8-byte aligned");
+    PolicyParams p = policy->p;
+    p.n = n;
+    p.goff = env_id_offset;
+    p.seed = seed;
+    p.step_index = step_index;
+    p.deterministic = deterministic != 0;
+    p.write_state = write_state != 0;
+    p.obs = obs;
+    p.start = episode_start;
+    p.h_pi = h_pi;
+    p.c_pi = c_pi;
+    p.h_vf = h_vf;
+    p.c_vf = c_vf;
+    p.actions = actions;
+    p.env_actions = env_actions;
+    p.values = values;
+    p.log_probs = log_probs;
+    p.mean_out = mean_out;
+    p.obs_norm_out = obs_norm_out;
+    const unsigned grid = (unsigned)((n + kTile - 1) / kTile);
+    hipLaunchKernelGGL(policy_step_kernel, dim3(grid, 2), dim3(kThreads), 0, (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) return fail(policy, HE_EHIP, "policy_step_kernel launch failed");
+    return HE_OK;
+}
+
+ha_status ha_gae(int64_t n, int64_t K, double gamma, double gae_lambda, const float* rewards, const float* values,
+                 const uint8_t* episode_starts, const float* last_values, const uint8_t* last_dones,
+                 float* advantages, float* returns, void* stream) {
+    ha_status st = check_gae(n, K, gamma, gae_lambda, rewards, values, episode_starts, last_values, last_dones,
+                             advantages, returns);
+    if (st != HE_OK) return st;
+    if (n > ((int64_t)1 << 30)) return fail_to(nullptr, HE_EINVAL, "n must be <= 2^30");
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(gae_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, n, K, (float)gamma,
+                       (float)(gamma * gae_lambda), rewards, values, episode_starts, last_values, last_dones, advantages,
+                       returns);
+    if (hipGetLastError() != hipSuccess) return fail_to(nullptr, HE_EHIP, "gae_kernel launch failed");
+    return HE_OK;
+}
+
+ha_status ha_host_policy_step(const ha_policy_weights* w, int64_t n, int64_t env_id_offset, uint64_t seed,
+                              uint64_t step_index, int32_t deterministic, int32_t write_state, const float* obs,
+                              const uint8_t* episode_start, float* h_pi, float* c_pi, float* h_vf, float* c_vf,
+                              float* actions, float* env_actions, float* values, float* log_probs, float* mean_out,
+                              float* obs_norm_out) {
+    ha_status st = check_policy_weights(w, nullptr);
+    if (st != HE_OK) return st;
+    if (n < 1 || env_id_offset < 0 || !obs || !episode_start || !h_pi || !c_pi || !h_vf || !c_vf || !actions ||
+        !env_actions || !values || !log_probs)
+        return fail((ha_policy*)nullptr, HE_EINVAL, "bad argument");
+    double sd[kObs], y[kObs];
+    if (w->obs_mean)
+        for (int k = 0; k < kObs; ++k) {
+            sd[k] = sqrt(w->obs_var[k] + w->epsilon);
+            y[k] = 1.0 / sd[k];
+        }
+    const bool relu = w->activation == HA_ACT_RELU;
+    const HostNet pi = actor_net(w), vf = critic_net(w);
+    const float stdv[kAct] = {policy_std(w->log_std[0]), policy_std(w->log_std[1])};
+    for (int64_t e = 0; e < n; ++e) {
+        float x[kObs], a2[kMlp], mean[kAct];
+        for (int k = 0; k < kObs; ++k) {
+            float v = obs[e * kObs + k];
+            if (w->obs_mean) v = norm_obs(v, w->obs_mean[k], sd[k], y[k], w->has_clip != 0, w->clip_obs);
+            if (obs_norm_out) obs_norm_out[e * kObs + k] = v;
+            x[k] = v;
+        }
+        const bool fresh = episode_start[e] != 0;
+        host_net_env(pi, x, fresh, h_pi + e * kHid, c_pi + e * kHid, write_state != 0, relu, a2);
+        for (int j = 0; j < kAct; ++j) {
+            mean[j] = host_head(pi, j, a2);
+            if (mean_out) mean_out[e * kAct + j] = mean[j];
+        }
+        host_net_env(vf, x, fresh, h_vf + e * kHid, c_vf + e * kHid, write_state != 0, relu, a2);
+        values[e] = host_head(vf, 0, a2);
+        sample_action(mean, w->log_std, stdv, seed, step_index, (uint64_t)(env_id_offset + e), deterministic != 0,
+                      actions + e * kAct, env_actions + e * kAct, log_probs + e);
+    }
+    return HE_OK;
+}
+
+ha_status ha_host_gae(int64_t n, int64_t K, double gamma, double gae_lambda, const float* rewards,
+                      const float* values, const uint8_t* episode_starts, const float* last_values,
+                      const uint8_t* last_dones, float* advantages, float* returns) {
+    ha_status st = check_gae(n, K, gamma, gae_lambda, rewards, values, episode_starts, last_values, last_dones,
+                             advantages, returns);
+    if (st != HE_OK) return st;
+    const float g32 = (float)gamma, gl32 = (float)(gamma * gae_lambda);
+    for (int64_t e = 0; e < n; ++e)
+        gae_env(e, n, K, g32, gl32, rewards, values, episode_starts, last_values, last_dones, advantages, returns);
+    return HE_OK;
+}
+
 }  // extern "C"
+

@@ -1,8 +1,9 @@
 /*
  * hedge_actor.h -- C ABI of libhedgeactor: the actor of an SB3 RecurrentPPO checkpoint
  * (sb3_contrib RecurrentActorCriticPolicy: obs 13 -> LSTM 128 -> Linear 64 -> Linear 64 ->
- * Linear 2) evaluated for N device-resident envs in one HIP kernel on MI355X (gfx950), and
- * the per-episode sums of a closed-loop evaluation around he_step.
+ * Linear 2) evaluated for N device-resident envs in one HIP kernel on MI355X (gfx950), the
+ * per-episode sums of a closed-loop evaluation around he_step, and the training side: actor,
+ * critic, action sampling and log-probability of a rollout step in one launch, and GAE.
  *
  * Conventions (as hedge_env.h): plain C types, every entry point returns an ha_status (the
  * he_status values), the last failure's message is ha_last_error(handle), no C++ exception
@@ -26,6 +27,35 @@
  *   5. two layers a = act(chain(bias; W in)), act = tanh (f32(tanh_f64)) or relu; then
  *      mean = chain(action_net).
  *   6. action = clip(mean, -1, 1) (HA_SQUASH_CLIP) or clip(f32(tanh_f64(mean)), -1, 1).
+ *
+ * Rollout collection (ha_policy_step, ha_gae: what sb3_contrib RecurrentPPO.collect_rollouts
+ * computes per step, and SB3 2.6.0 RolloutBuffer.compute_returns_and_advantage after it;
+ * restated, SB3 is not a dependency).  Per env e:
+ *   P1. steps 1-5 with the actor's tensors and h_pi / c_pi give mean[2]: for the same tensors
+ *       the bits of ha_step's mean_out.
+ *   P2. steps 1-5 with the critic's LSTM (lstm_critic) and MLP (value_net, the same
+ *       activation) on the same normalised obs and the critic's own h_vf / c_vf give a2[64];
+ *       value = chain(vb3; v3 a2), the k-ordered fmaf chain of 64 terms.
+ *   P3. std[j] = f32(exp_f64(f64(log_std[j]))).
+ *   P4. noise: one Philox4x32-10 block, counter (lo(step_index), hi(step_index), lo(g), hi(g))
+ *       with g = env_id_offset + e, key (lo(seed), hi(seed)): the env's own layout, so the
+ *       caller passes a seed distinct from the env's.  u1 = u01(x0, x1), u2 = u01(x2, x3),
+ *       (z0, z1) = box_muller(u1, u2) in f64, eps[j] = f32(z_j).  Nothing depends on how the
+ *       envs are split over calls or ranks.
+ *   P5. a[j] = deterministic ? mean[j] : fmaf(std[j], eps[j], mean[j]);
+ *       env_action[j] = clip(a[j], -1, 1).
+ *   P6. log_prob = f32(sum_j ((-0.5 z_j^2 - f64(log_std[j])) - 0.9189385332046727)), f64, j in
+ *       order from 0, with z_j = (f64(a[j]) - f64(mean[j])) / f64(std[j]):
+ *       torch.distributions.Normal(mean, std).log_prob(a).sum(-1), rounded once.
+ *   P7. GAE, f32 throughout, no contraction; g32 = f32(gamma), gl32 = f32(gamma gae_lambda)
+ *       (the product in f64).  last = 0; for k = K-1 .. 0:
+ *         nnt   = 1 - f32(last_dones)          at k = K-1, else 1 - f32(episode_starts[k+1])
+ *         nv    = last_values                  at k = K-1, else values[k+1]
+ *         delta = ((rewards[k] + ((g32 nv) nnt)) - values[k])
+ *         last  = delta + ((gl32 nnt) last)
+ *         advantages[k] = last; returns[k] = last + values[k]
+ *       The env never truncates an episode (it ends by `terminated` only), so SB3's time-out
+ *       bootstrap (reward += gamma V(terminal_obs)) has no counterpart here.
  */
 #ifndef HEDGE_ACTOR_H
 #define HEDGE_ACTOR_H
@@ -118,6 +148,89 @@ ha_status ha_accumulate(ha_actor* actor, int64_t n, int64_t env_id_offset, const
 /* ha_step's arithmetic on the host, HOST pointers, straight from the unpacked tensors. */
 ha_status ha_host_step(const ha_weights* w, int64_t n, const float* obs, const uint8_t* episode_start, float* h,
                        float* c, float* actions, float* mean_out, float* obs_norm_out);
+
+/* ---- rollout collection: actor + critic + sampling in one launch, and GAE ---- */
+#define HA_POLICY_ABI_VERSION 1
+
+/* Actor and critic of the checkpoint: HOST pointers, torch layout.  log_std is required. */
+typedef struct ha_policy_weights {
+    int32_t abi_version;   /* HA_POLICY_ABI_VERSION */
+    int32_t obs_dim;       /* 13 */
+    int32_t hidden;        /* 128, actor and critic */
+    int32_t n_lstm_layers; /* 1 */
+    int32_t mlp_width;     /* 64 */
+    int32_t act_dim;       /* 2 */
+    int32_t activation;    /* ha_activation, both MLPs */
+    int32_t has_clip;
+    double clip_obs;
+    double epsilon;
+    const double* obs_mean; /* [13] or NULL: both NULL = no normalisation */
+    const double* obs_var;
+    const float* w_ih;     /* the actor, as ha_weights */
+    const float* w_hh;
+    const float* b_ih;
+    const float* b_hh;
+    const float* w1;
+    const float* b1;
+    const float* w2;
+    const float* b2;
+    const float* w3;
+    const float* b3;
+    const float* log_std;  /* [2] */
+    const float* c_w_ih;   /* lstm_critic.weight_ih_l0 [512][13]  */
+    const float* c_w_hh;   /* lstm_critic.weight_hh_l0 [512][128] */
+    const float* c_b_ih;   /* lstm_critic.bias_ih_l0   [512]      */
+    const float* c_b_hh;   /* lstm_critic.bias_hh_l0   [512]      */
+    const float* v1;       /* mlp_extractor.value_net.0.weight [64][128] */
+    const float* vb1;      /* mlp_extractor.value_net.0.bias   [64]      */
+    const float* v2;       /* mlp_extractor.value_net.2.weight [64][64]  */
+    const float* vb2;      /* mlp_extractor.value_net.2.bias   [64]      */
+    const float* v3;       /* value_net.weight [1][64] */
+    const float* vb3;      /* value_net.bias   [1]     */
+} ha_policy_weights;
+
+typedef struct ha_policy ha_policy;
+
+/* The last failure's message on `policy`; NULL = the last failed ha_policy_create /
+ * ha_host_policy_step / ha_host_gae / ha_gae of this thread. */
+const char* ha_policy_last_error(const ha_policy* policy);
+
+/* As ha_create / ha_destroy: anything but 13 / 128 x 1 layer / 64-64 / 2 actions / 1 value is
+ * HE_ESHAPE with a message; both networks are packed in ha_create's fragment order. */
+ha_status ha_policy_create(const ha_policy_weights* w, ha_policy** out);
+ha_status ha_policy_destroy(ha_policy* policy);
+
+/* Re-packs and re-uploads every tensor and statistic of an existing handle (a training loop
+ * changes them after each rollout).  SYNCHRONISES: it waits for the device to go idle, so no
+ * step in flight reads half-written weights, and copies synchronously.  Not capturable. */
+ha_status ha_policy_update(ha_policy* policy, const ha_policy_weights* w);
+
+/* One collection step of n envs (contract P1-P6), one launch, DEVICE pointers, no host
+ * synchronisation.  obs [n][13], episode_start [n] u8; h_pi, c_pi, h_vf, c_vf [n][128] are
+ * updated in place (16-byte aligned) unless write_state = 0, which computes every output and
+ * stores no state: SB3's predict_values call for last_values.  Out: actions [n][2] unclipped
+ * (what the buffer stores), env_actions [n][2] clipped to +-1 (what the env is fed), values
+ * [n], log_probs [n]; mean_out [n][2] and obs_norm_out [n][13] may be NULL. */
+ha_status ha_policy_step(ha_policy* policy, int64_t n, int64_t env_id_offset, uint64_t seed, uint64_t step_index,
+                         int32_t deterministic, int32_t write_state, const float* obs, const uint8_t* episode_start,
+                         float* h_pi, float* c_pi, float* h_vf, float* c_vf, float* actions, float* env_actions,
+                         float* values, float* log_probs, float* mean_out, float* obs_norm_out, void* stream);
+
+/* Contract P7 over DEVICE arrays laid out [K][n] (SB3's (buffer_size, n_envs)): one thread per
+ * env walks k from K-1 down to 0, every access coalesced over the env index. */
+ha_status ha_gae(int64_t n, int64_t K, double gamma, double gae_lambda, const float* rewards, const float* values,
+                 const uint8_t* episode_starts, const float* last_values, const uint8_t* last_dones,
+                 float* advantages, float* returns, void* stream);
+
+/* The same arithmetic on the host, HOST pointers, straight from the unpacked tensors. */
+ha_status ha_host_policy_step(const ha_policy_weights* w, int64_t n, int64_t env_id_offset, uint64_t seed,
+                              uint64_t step_index, int32_t deterministic, int32_t write_state, const float* obs,
+                              const uint8_t* episode_start, float* h_pi, float* c_pi, float* h_vf, float* c_vf,
+                              float* actions, float* env_actions, float* values, float* log_probs, float* mean_out,
+                              float* obs_norm_out);
+ha_status ha_host_gae(int64_t n, int64_t K, double gamma, double gae_lambda, const float* rewards,
+                      const float* values, const uint8_t* episode_starts, const float* last_values,
+                      const uint8_t* last_dones, float* advantages, float* returns);
 
 #ifdef __cplusplus
 }
