@@ -10,6 +10,9 @@ reference's Python interface on top:
   include/hedge_actor.h, libhedgeactor.so), `HedgingVecEnv.evaluate_actor` around it
 * `RecurrentPolicy`, `RolloutCollector` -- actor + critic + sampling + log-prob per step in one
   kernel and GAE: RecurrentPPO's collect_rollouts on the device (agent.py, collect.py)
+* `lstm_sequence`, `lstm_sequence_pair`, `RecurrentPPOModule`, `ppo_update` -- the LSTM over a stored
+  sequence with per-step resets as a differentiable op (one forward and one backward kernel for actor
+  and critic), evaluate_actions and RecurrentPPO.train's loss on top of it (train.py)
 """
 __version__ = "0.1.0"
 
@@ -30,4 +33,7 @@ def __getattr__(name):
     if name == "RolloutCollector":
         from .collect import RolloutCollector
         return RolloutCollector
+    if name in ("lstm_sequence", "lstm_sequence_pair", "RecurrentPPOModule", "ppo_update"):
+        from . import train
+        return getattr(train, name)
     raise AttributeError(name)

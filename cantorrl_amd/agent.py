@@ -69,7 +69,8 @@ HA_POLICY_ABI_VERSION = 1
 
 EXPORTS = ["ha_version", "ha_last_error", "ha_create", "ha_destroy", "ha_step", "ha_accumulate", "ha_host_step",
            "ha_policy_last_error", "ha_policy_create", "ha_policy_destroy", "ha_policy_update", "ha_policy_step",
-           "ha_gae", "ha_host_policy_step", "ha_host_gae"]
+           "ha_gae", "ha_host_policy_step", "ha_host_gae", "ha_lstm_seq_workspace_bytes", "ha_lstm_seq_forward",
+           "ha_lstm_seq_backward", "ha_host_lstm_seq_forward", "ha_host_lstm_seq_backward"]
 
 _F = ctypes.POINTER(ctypes.c_float)
 _D = ctypes.POINTER(ctypes.c_double)
@@ -124,6 +125,11 @@ def load(path=LIB_PATH):
         "ha_gae": (i32, [i64, i64, f64, f64] + [vp] * 8),
         "ha_host_policy_step": (i32, [PW, i64, i64, u64, u64, i32, i32] + [vp] * 12),
         "ha_host_gae": (i32, [i64, i64, f64, f64] + [vp] * 7),
+        "ha_lstm_seq_workspace_bytes": (ctypes.c_size_t, [i64]),
+        "ha_lstm_seq_forward": (i32, [i64, i64, i64] + [vp] * 5),
+        "ha_lstm_seq_backward": (i32, [i64, i64, i64] + [vp] * 4),
+        "ha_host_lstm_seq_forward": (i32, [i64, i64, i64] + [vp] * 3),
+        "ha_host_lstm_seq_backward": (i32, [i64, i64, i64] + [vp] * 2),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -53,6 +53,49 @@ HE_HD float cell_update(float pi, float pf, float pg, float po, float* c) {
     return o * tanhf_r(cn);
 }
 
+// cell_update that also hands out the four activations (contract F2): the same operations in the
+// same order, so c' and h' are cell_update's bits
+HE_HD float cell_forward(float pi, float pf, float pg, float po, float* c, float* gate) {
+    const float i = sigmoidf_r(pi), f = sigmoidf_r(pf), o = sigmoidf_r(po);
+    const float g = tanhf_r(pg);
+    const float fc = f * *c;
+    const float ig = i * g;
+    const float cn = fc + ig;
+    *c = cn;
+    gate[0] = i, gate[1] = f, gate[2] = g, gate[3] = o;
+    return o * tanhf_r(cn);
+}
+
+// Contract B2-B3 for one (unit, env) at one step: the gradient of the four pre-activations into
+// dgate[i, f, g, o]; returns dct f, the cell carry of the step before (the caller zeroes it at an
+// episode start).  One f32 rounding per line.
+HE_HD float cell_backward(float i, float f, float g, float o, float ct, float c_prev, float dh, float dc,
+                          float* dgate) {
+    const float tc = tanhf_r(ct);
+    const float tc2 = tc * tc;
+    const float omt = 1.0f - tc2;
+    const float dho = dh * o;
+    const float dhc = dho * omt;
+    const float dct = dhc + dc;
+    const float i1 = 1.0f - i;
+    const float ii = i * i1;
+    const float f1 = 1.0f - f;
+    const float ff = f * f1;
+    const float g2 = g * g;
+    const float gg = 1.0f - g2;
+    const float o1 = 1.0f - o;
+    const float oo = o * o1;
+    const float dg_i = dct * g;
+    const float dg_f = dct * c_prev;
+    const float dg_g = dct * i;
+    const float dg_o = dh * tc;
+    dgate[0] = dg_i * ii;
+    dgate[1] = dg_f * ff;
+    dgate[2] = dg_g * gg;
+    dgate[3] = dg_o * oo;
+    return dct * f;
+}
+
 HE_HD float mlp_act(float x, bool relu) { return relu ? (x > 0.0f ? x : (x != x ? x : 0.0f)) : tanhf_r(x); }
 
 HE_HD float squash_action(float mean, bool tanh_squash) {

@@ -24,7 +24,8 @@
 // blockIdx.y = 0 runs the actor's packed tensors on h_pi / c_pi and ends in the sampling and the
 // log-probability, blockIdx.y = 1 runs the critic's on h_vf / c_vf and ends in the value.  Both
 // stage the same obs; registers and LDS stay at actor_kernel's figures.  gae_kernel (ha_gae) is
-// one thread per env over [K][n] arrays.
+// one thread per env over [K][n] arrays.  lstm_seq_fwd_kernel / lstm_seq_bwd_kernel (the PPO update's
+// LSTM over a stored sequence, forward and backward) are described where they stand.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -533,6 +534,309 @@ ha_status check_gae(int64_t n, int64_t K, double gamma, double gae_lambda, const
     return HE_OK;
 }
 
+// ---------------------------------------------------------------- the LSTM over a stored sequence
+// lstm_seq_fwd_kernel / lstm_seq_bwd_kernel (ha_lstm_seq_forward / _backward, contract F1-F2 and
+// B1-B4): grid (tiles, n_nets), a workgroup of 4 waves owns 32 envs of one network for ALL L steps.
+//   forward   net_tile's gate section per step; c stays in registers, h' goes to the OTHER half of a
+//             double-buffered xh (zeroed where the next step starts an episode) beside the next
+//             step's x, so one barrier per step orders the B-operand reads against the writes.
+//   backward  the cell backward in registers on the forward's (unit, env) ownership; d_gates[t] to
+//             HBM and to LDS as dg[u][env]; dh_rec = W_hh^T d_gates as ONE accumulator per wave
+//             (output units 32 w .. 32 w + 31) over 256 k-steps of 32x32x2: the k-ordered chain over
+//             u = 0 .. 511.  Two barriers per step (dg written / dg read).
+// The weights arrive as device tensors in torch layout and are packed into the workspace by a small
+// kernel in front of each launch: [wg | bg | wt] per network, wg / bg as pack_net's, wt[w][s][lane] =
+// w_hh[2 s + (lane >> 5)][32 w + (lane & 31)].
+constexpr int kStepsB = kGates / 2;   // 256 k-steps of the recurrent gradient
+constexpr size_t kSeqBg = n_wg, kSeqWt = kSeqBg + kGates, kSeqNetFloats = kSeqWt + (size_t)4 * kStepsB * 64;
+static_assert(kSeqBg % 4 == 0 && kSeqWt % 4 == 0 && kSeqNetFloats % 4 == 0, "16-byte aligned sections");
+
+struct SeqPackParams {
+    const float* w_ih[2];
+    const float* w_hh[2];
+    const float* b_ih[2];
+    const float* b_hh[2];
+    float* ws;
+};
+
+struct SeqFwdParams {
+    int64_t L, B;
+    const float* x;
+    const uint8_t* start;
+    ha_lstm_seq_net net[2];
+    const float* ws;
+};
+
+struct SeqBwdParams {
+    int64_t L, B;
+    const uint8_t* start;
+    ha_lstm_seq_bwd net[2];
+    const float* ws;
+};
+
+// grid (blocks, n_nets): the forward's sections
+__global__ __launch_bounds__(256) void lstm_seq_pack_fwd_kernel(const SeqPackParams p) {
+    const bool second = blockIdx.y != 0;
+    const float* __restrict__ w_ih = second ? p.w_ih[1] : p.w_ih[0];
+    const float* __restrict__ w_hh = second ? p.w_hh[1] : p.w_hh[0];
+    const float* __restrict__ b_ih = second ? p.b_ih[1] : p.b_ih[0];
+    const float* __restrict__ b_hh = second ? p.b_hh[1] : p.b_hh[0];
+    float* dst = p.ws + (second ? kSeqNetFloats : 0);
+    for (unsigned idx = blockIdx.x * 256 + threadIdx.x; idx < kSeqWt; idx += gridDim.x * 256) {
+        float v;
+        if (idx < kSeqBg) {
+            const int g = idx & 3, l = (idx >> 2) & 63;
+            const int rest = idx >> 8, ug = rest / kStepsG, s = rest - ug * kStepsG;
+            const int j = g * kHid + ug * 32 + (l & 31), k = 2 * s + (l >> 5);
+            v = k < kObs ? w_ih[j * kObs + k] : (k < kKx ? w_hh[j * kHid + (k - kObs)] : 0.0f);
+        } else {
+            const int j = idx - kSeqBg;
+            v = b_ih[j] + b_hh[j];
+        }
+        dst[idx] = v;
+    }
+}
+
+// grid (blocks, n_nets): the backward's section, W_hh transposed in fragment order
+__global__ __launch_bounds__(256) void lstm_seq_pack_bwd_kernel(const SeqPackParams p) {
+    const bool second = blockIdx.y != 0;
+    const float* __restrict__ w_hh = second ? p.w_hh[1] : p.w_hh[0];
+    float* dst = p.ws + (second ? kSeqNetFloats : 0) + kSeqWt;
+    for (unsigned idx = blockIdx.x * 256 + threadIdx.x; idx < 4u * kStepsB * 64; idx += gridDim.x * 256) {
+        const int l = idx & 63, s = (idx >> 6) & (kStepsB - 1), w = idx >> 14;
+        dst[idx] = w_hh[(2 * s + (l >> 5)) * kHid + w * 32 + (l & 31)];
+    }
+}
+
+struct SeqTile {
+    float xh[2][kKp][kLd];   // 37,488 B: step t reads [t & 1] and fills [(t + 1) & 1]
+};
+
+__global__ __launch_bounds__(kThreads, 2) void lstm_seq_fwd_kernel(const SeqFwdParams p) {
+    __shared__ SeqTile t;
+    const int tid = threadIdx.x;
+    const int64_t B = p.B, L = p.L;
+    const int64_t e0 = (int64_t)blockIdx.x * kTile;
+    const bool second = blockIdx.y != 0;
+    const ha_lstm_seq_net nt = second ? p.net[1] : p.net[0];
+    const float* ws = p.ws + (second ? kSeqNetFloats : 0);
+    const float* __restrict__ bg = ws + kSeqBg;
+    const uint8_t* __restrict__ start = p.start;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int col = lane & 31, hi = lane >> 5;
+    const int64_t e = e0 + col;
+    const bool valid = e < B;
+    const int nx = (int)((B - e0 < kTile ? B - e0 : kTile) * kObs);   // the tile's x of one step: contiguous
+    const int el0 = tid / kObs, k0 = tid - el0 * kObs;
+    const int el1 = (tid + kThreads) / kObs, k1 = (tid + kThreads) - el1 * kObs;
+
+    // ---- step 0's operand: [x[0] | h0, zeroed at a start | 0]; the padding row of both halves
+    {
+        const float* x0 = p.x + e0 * kObs;
+        t.xh[0][k0][el0] = tid < nx ? x0[tid] : 0.0f;
+        if (tid + kThreads < kTile * kObs) t.xh[0][k1][el1] = tid + kThreads < nx ? x0[tid + kThreads] : 0.0f;
+        for (int idx = tid; idx < kTile * kHid; idx += kThreads) {
+            const int el = idx >> 7, u = idx & (kHid - 1);
+            float v = 0.0f;
+            if (e0 + el < B && !start[e0 + el]) v = nt.h0[(e0 + el) * kHid + u];
+            t.xh[0][kObs + u][el] = v;
+        }
+        if (tid < 2 * kTile) t.xh[tid >> 5][kKx][tid & 31] = 0.0f;
+    }
+    float cc[16];
+    {
+        const bool fresh = valid && start[e] != 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float4 cv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (valid && !fresh) cv = *(const float4*)(nt.c0 + e * kHid + wave * 32 + 8 * q + 4 * hi);
+            cc[4 * q + 0] = cv.x; cc[4 * q + 1] = cv.y; cc[4 * q + 2] = cv.z; cc[4 * q + 3] = cv.w;
+        }
+    }
+    __syncthreads();
+
+    const float4* wp = (const float4*)ws + (size_t)wave * kStepsG * 64 + lane;
+    for (int64_t ts = 0; ts < L; ++ts) {
+        const int cur = (int)(ts & 1), nxt = cur ^ 1;
+        const bool more = ts + 1 < L;
+        // the next step's x and start flag: issued now, used after the gate product
+        float xv0 = 0.0f, xv1 = 0.0f;
+        bool nfresh = false;
+        if (more) {
+            const float* xn = p.x + ((ts + 1) * B + e0) * kObs;
+            if (tid < nx) xv0 = xn[tid];
+            if (tid + kThreads < nx) xv1 = xn[tid + kThreads];
+            nfresh = valid && start[(ts + 1) * B + e] != 0;
+        }
+        // weights and bias are re-read every step (L2 hits): loop-invariant loads hoisted out of
+        // the step loop would sit in registers and spill
+        const float* bgs = bg;
+        const float4* wps = wp;
+        asm volatile("" : "+s"(bgs), "+v"(wps));
+        f32x16 acc[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float4 b = *(const float4*)(bgs + g * kHid + wave * 32 + 8 * q + 4 * hi);
+                acc[g][4 * q + 0] = b.x; acc[g][4 * q + 1] = b.y; acc[g][4 * q + 2] = b.z; acc[g][4 * q + 3] = b.w;
+            }
+#pragma unroll 4
+        for (int s = 0; s < kStepsG; ++s) {
+            const float4 w = wps[s * 64];
+            const float b = t.xh[cur][2 * s + hi][col];
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, b, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, b, acc[1], 0, 0, 0);
+            acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, b, acc[2], 0, 0, 0);
+            acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, b, acc[3], 0, 0, 0);
+        }
+        // ---- cell update in registers; h', c', gates leave as 16-byte lines
+        const int64_t row = ts * B + e;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int u = wave * 32 + 8 * q + 4 * hi;
+            float hv[4], gt[4][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int r = 4 * q + j;
+                hv[j] = cell_forward(acc[0][r], acc[1][r], acc[2][r], acc[3][r], &cc[r], gt[j]);
+                if (more) t.xh[nxt][kObs + u + j][col] = nfresh ? 0.0f : hv[j];
+            }
+            if (valid) {
+                *(float4*)(nt.h + row * kHid + u) = make_float4(hv[0], hv[1], hv[2], hv[3]);
+                *(float4*)(nt.c + row * kHid + u) = make_float4(cc[4 * q], cc[4 * q + 1], cc[4 * q + 2], cc[4 * q + 3]);
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    *(float4*)(nt.gates + (row * 4 + g) * kHid + u) = make_float4(gt[0][g], gt[1][g], gt[2][g], gt[3][g]);
+            }
+            if (nfresh) cc[4 * q] = cc[4 * q + 1] = cc[4 * q + 2] = cc[4 * q + 3] = 0.0f;
+        }
+        if (more) {
+            t.xh[nxt][k0][el0] = xv0;
+            if (tid + kThreads < kTile * kObs) t.xh[nxt][k1][el1] = xv1;
+        }
+        __syncthreads();
+    }
+}
+
+struct SeqBwdTile {
+    float dg[kGates][kLd];   // 67,584 B: d_gates[t] of the tile, the B operand of the recurrent gradient
+};
+
+__global__ __launch_bounds__(kThreads, 2) void lstm_seq_bwd_kernel(const SeqBwdParams p) {
+    __shared__ SeqBwdTile t;
+    const int tid = threadIdx.x;
+    const int64_t B = p.B, L = p.L;
+    const int64_t e0 = (int64_t)blockIdx.x * kTile;
+    const bool second = blockIdx.y != 0;
+    const ha_lstm_seq_bwd nt = second ? p.net[1] : p.net[0];
+    const uint8_t* __restrict__ start = p.start;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int col = lane & 31, hi = lane >> 5;
+    const int64_t e = e0 + col;
+    const bool valid = e < B;
+    const float* __restrict__ wt = p.ws + (second ? kSeqNetFloats : 0) + kSeqWt + (size_t)wave * kStepsB * 64 + lane;
+
+    float dc[16], dhr[16], cur[16];   // the carries, and c[t] on its way down
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        float4 cv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (valid) cv = *(const float4*)(nt.c + ((L - 1) * B + e) * kHid + wave * 32 + 8 * q + 4 * hi);
+        cur[4 * q + 0] = cv.x; cur[4 * q + 1] = cv.y; cur[4 * q + 2] = cv.z; cur[4 * q + 3] = cv.w;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dc[r] = dhr[r] = 0.0f;
+
+    for (int64_t ts = L - 1; ts >= 0; --ts) {
+        const int64_t row = ts * B + e;
+        const bool fresh = valid && start[row] != 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int u = wave * 32 + 8 * q + 4 * hi;
+            const float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            float4 dh4 = z4, pv4 = z4, g4[4] = {z4, z4, z4, z4};
+            if (valid) {
+                dh4 = *(const float4*)(nt.d_h + row * kHid + u);
+                pv4 = ts > 0 ? *(const float4*)(nt.c + (row - B) * kHid + u) : *(const float4*)(nt.c0 + e * kHid + u);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) g4[g] = *(const float4*)(nt.gates + (row * 4 + g) * kHid + u);
+            }
+            const float dhv[4] = {dh4.x, dh4.y, dh4.z, dh4.w}, pv[4] = {pv4.x, pv4.y, pv4.z, pv4.w};
+            const float gi[4] = {g4[0].x, g4[0].y, g4[0].z, g4[0].w}, gf[4] = {g4[1].x, g4[1].y, g4[1].z, g4[1].w};
+            const float gg[4] = {g4[2].x, g4[2].y, g4[2].z, g4[2].w}, go[4] = {g4[3].x, g4[3].y, g4[3].z, g4[3].w};
+            float d[4][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int r = 4 * q + j;
+                const float dh = dhv[j] + dhr[r];
+                const float dcn = cell_backward(gi[j], gf[j], gg[j], go[j], cur[r], fresh ? 0.0f : pv[j], dh, dc[r], d[j]);
+                dc[r] = fresh ? 0.0f : dcn;
+                cur[r] = pv[j];
+#pragma unroll
+                for (int g = 0; g < 4; ++g) t.dg[g * kHid + u + j][col] = d[j][g];
+            }
+            if (valid) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    *(float4*)(nt.d_gates + (row * 4 + g) * kHid + u) = make_float4(d[0][g], d[1][g], d[2][g], d[3][g]);
+            }
+        }
+        if (ts == 0) break;   // h0 receives no gradient
+        __syncthreads();
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+#pragma unroll 8
+        for (int s = 0; s < kStepsB; ++s)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wt[s * 64], t.dg[2 * s + hi][col], acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dhr[r] = fresh ? 0.0f : acc[r];
+        __syncthreads();
+    }
+}
+
+ha_status check_seq(int64_t n_nets, int64_t L, int64_t B) {
+    char m[200];
+    if (n_nets != 1 && n_nets != 2) {
+        snprintf(m, sizeof m, "n_nets = %lld: one network or the actor / critic pair", (long long)n_nets);
+        return fail_to(nullptr, HE_ESHAPE, m);
+    }
+    if (L < 1 || B < 1 || B > ((int64_t)1 << 30) || L > ((int64_t)1 << 30)) {
+        snprintf(m, sizeof m, "sequence of L = %lld steps x B = %lld envs: both must be in [1, 2^30]", (long long)L,
+                 (long long)B);
+        return fail_to(nullptr, HE_ESHAPE, m);
+    }
+    return HE_OK;
+}
+
+inline bool bad_ptr(const void* q, uintptr_t mask) { return !q || (((uintptr_t)q) & mask); }
+
+ha_status check_seq_fwd(int64_t n_nets, const void* x, const void* starts, const ha_lstm_seq_net* nets, uintptr_t mask) {
+    if (!nets) return fail_to(nullptr, HE_EINVAL, "nets is NULL");
+    if (bad_ptr(x, mask) || bad_ptr(starts, mask))
+        return fail_to(nullptr, HE_EINVAL, "x and episode_starts must be non-NULL and 16-byte aligned");
+    for (int64_t k = 0; k < n_nets; ++k) {
+        const ha_lstm_seq_net& n = nets[k];
+        if (bad_ptr(n.w_ih, mask) || bad_ptr(n.w_hh, mask) || bad_ptr(n.b_ih, mask) || bad_ptr(n.b_hh, mask) ||
+            bad_ptr(n.h0, mask) || bad_ptr(n.c0, mask) || bad_ptr(n.h, mask) || bad_ptr(n.c, mask) ||
+            bad_ptr(n.gates, mask))
+            return fail_to(nullptr, HE_EINVAL, "a tensor of ha_lstm_seq_net is NULL or not 16-byte aligned");
+    }
+    return HE_OK;
+}
+
+ha_status check_seq_bwd(int64_t n_nets, const void* starts, const ha_lstm_seq_bwd* nets, uintptr_t mask) {
+    if (!nets) return fail_to(nullptr, HE_EINVAL, "nets is NULL");
+    if (bad_ptr(starts, mask)) return fail_to(nullptr, HE_EINVAL, "episode_starts must be non-NULL and 16-byte aligned");
+    for (int64_t k = 0; k < n_nets; ++k) {
+        const ha_lstm_seq_bwd& n = nets[k];
+        if (bad_ptr(n.w_hh, mask) || bad_ptr(n.c0, mask) || bad_ptr(n.c, mask) || bad_ptr(n.gates, mask) ||
+            bad_ptr(n.d_h, mask) || bad_ptr(n.d_gates, mask))
+            return fail_to(nullptr, HE_EINVAL, "a tensor of ha_lstm_seq_bwd is NULL or not 16-byte aligned");
+    }
+    return HE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -811,6 +1115,150 @@ ha_status ha_host_gae(int64_t n, int64_t K, double gamma, double gae_lambda, con
     const float g32 = (float)gamma, gl32 = (float)(gamma * gae_lambda);
     for (int64_t e = 0; e < n; ++e)
         gae_env(e, n, K, g32, gl32, rewards, values, episode_starts, last_values, last_dones, advantages, returns);
+    return HE_OK;
+}
+
+size_t ha_lstm_seq_workspace_bytes(int64_t n_nets) {
+    return (n_nets == 1 || n_nets == 2) ? (size_t)n_nets * kSeqNetFloats * sizeof(float) : 0;
+}
+
+ha_status ha_lstm_seq_forward(int64_t n_nets, int64_t L, int64_t B, const float* x, const uint8_t* episode_starts,
+                              const ha_lstm_seq_net* nets, void* workspace, void* stream) {
+    ha_status st = check_seq(n_nets, L, B);
+    if (st != HE_OK) return st;
+    st = check_seq_fwd(n_nets, x, episode_starts, nets, 15u);
+    if (st != HE_OK) return st;
+    if (bad_ptr(workspace, 15u)) return fail_to(nullptr, HE_EINVAL, "workspace must be non-NULL and 16-byte aligned");
+    SeqPackParams pk;
+    SeqFwdParams p;
+    memset(&pk, 0, sizeof pk);
+    memset(&p, 0, sizeof p);
+    for (int64_t k = 0; k < n_nets; ++k) {
+        pk.w_ih[k] = nets[k].w_ih;
+        pk.w_hh[k] = nets[k].w_hh;
+        pk.b_ih[k] = nets[k].b_ih;
+        pk.b_hh[k] = nets[k].b_hh;
+        p.net[k] = nets[k];
+    }
+    pk.ws = (float*)workspace;
+    p.L = L;
+    p.B = B;
+    p.x = x;
+    p.start = episode_starts;
+    p.ws = (const float*)workspace;
+    hipLaunchKernelGGL(lstm_seq_pack_fwd_kernel, dim3(72, (unsigned)n_nets), dim3(256), 0, (hipStream_t)stream, pk);
+    if (hipGetLastError() != hipSuccess) return fail_to(nullptr, HE_EHIP, "lstm_seq_pack_fwd_kernel launch failed");
+    const unsigned grid = (unsigned)((B + kTile - 1) / kTile);
+    hipLaunchKernelGGL(lstm_seq_fwd_kernel, dim3(grid, (unsigned)n_nets), dim3(kThreads), 0, (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) return fail_to(nullptr, HE_EHIP, "lstm_seq_fwd_kernel launch failed");
+    return HE_OK;
+}
+
+ha_status ha_lstm_seq_backward(int64_t n_nets, int64_t L, int64_t B, const uint8_t* episode_starts,
+                               const ha_lstm_seq_bwd* nets, void* workspace, void* stream) {
+    ha_status st = check_seq(n_nets, L, B);
+    if (st != HE_OK) return st;
+    st = check_seq_bwd(n_nets, episode_starts, nets, 15u);
+    if (st != HE_OK) return st;
+    if (bad_ptr(workspace, 15u)) return fail_to(nullptr, HE_EINVAL, "workspace must be non-NULL and 16-byte aligned");
+    SeqPackParams pk;
+    SeqBwdParams p;
+    memset(&pk, 0, sizeof pk);
+    memset(&p, 0, sizeof p);
+    for (int64_t k = 0; k < n_nets; ++k) {
+        pk.w_hh[k] = nets[k].w_hh;
+        p.net[k] = nets[k];
+    }
+    pk.ws = (float*)workspace;
+    p.L = L;
+    p.B = B;
+    p.start = episode_starts;
+    p.ws = (const float*)workspace;
+    hipLaunchKernelGGL(lstm_seq_pack_bwd_kernel, dim3(64, (unsigned)n_nets), dim3(256), 0, (hipStream_t)stream, pk);
+    if (hipGetLastError() != hipSuccess) return fail_to(nullptr, HE_EHIP, "lstm_seq_pack_bwd_kernel launch failed");
+    const unsigned grid = (unsigned)((B + kTile - 1) / kTile);
+    hipLaunchKernelGGL(lstm_seq_bwd_kernel, dim3(grid, (unsigned)n_nets), dim3(kThreads), 0, (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) return fail_to(nullptr, HE_EHIP, "lstm_seq_bwd_kernel launch failed");
+    return HE_OK;
+}
+
+ha_status ha_host_lstm_seq_forward(int64_t n_nets, int64_t L, int64_t B, const float* x,
+                                   const uint8_t* episode_starts, const ha_lstm_seq_net* nets) {
+    ha_status st = check_seq(n_nets, L, B);
+    if (st != HE_OK) return st;
+    st = check_seq_fwd(n_nets, x, episode_starts, nets, 0u);
+    if (st != HE_OK) return st;
+    for (int64_t k = 0; k < n_nets; ++k) {
+        const ha_lstm_seq_net& n = nets[k];
+        const HostNet w = {n.w_ih, n.w_hh, n.b_ih, n.b_hh, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+        for (int64_t e = 0; e < B; ++e) {
+            float h[kHid], c[kHid], hn[kHid], xh[kKp];
+            memcpy(h, n.h0 + e * kHid, sizeof h);
+            memcpy(c, n.c0 + e * kHid, sizeof c);
+            for (int64_t t = 0; t < L; ++t) {
+                const int64_t row = t * B + e;
+                const bool fresh = episode_starts[row] != 0;
+                for (int i = 0; i < kObs; ++i) xh[i] = x[row * kObs + i];
+                for (int u = 0; u < kHid; ++u) xh[kObs + u] = fresh ? 0.0f : h[u];
+                xh[kKx] = 0.0f;
+                for (int u = 0; u < kHid; ++u) {
+                    float pre[4], gt[4];
+                    for (int g = 0; g < 4; ++g) {
+                        const int j = g * kHid + u;
+                        float acc = n.b_ih[j] + n.b_hh[j];
+                        for (int i = 0; i < kKp; ++i) acc = fmaf(gate_w(w, j, i), xh[i], acc);
+                        pre[g] = acc;
+                    }
+                    float cv = fresh ? 0.0f : c[u];
+                    hn[u] = cell_forward(pre[0], pre[1], pre[2], pre[3], &cv, gt);
+                    c[u] = cv;
+                    for (int g = 0; g < 4; ++g) n.gates[(row * 4 + g) * kHid + u] = gt[g];
+                }
+                memcpy(h, hn, sizeof h);
+                memcpy(n.h + row * kHid, h, sizeof h);
+                memcpy(n.c + row * kHid, c, sizeof c);
+            }
+        }
+    }
+    return HE_OK;
+}
+
+ha_status ha_host_lstm_seq_backward(int64_t n_nets, int64_t L, int64_t B, const uint8_t* episode_starts,
+                                    const ha_lstm_seq_bwd* nets) {
+    ha_status st = check_seq(n_nets, L, B);
+    if (st != HE_OK) return st;
+    st = check_seq_bwd(n_nets, episode_starts, nets, 0u);
+    if (st != HE_OK) return st;
+    std::vector<float> dgv(kGates);
+    float* dg = dgv.data();
+    for (int64_t k = 0; k < n_nets; ++k) {
+        const ha_lstm_seq_bwd& n = nets[k];
+        for (int64_t e = 0; e < B; ++e) {
+            float dc[kHid], dhr[kHid];
+            for (int u = 0; u < kHid; ++u) dc[u] = dhr[u] = 0.0f;
+            for (int64_t t = L - 1; t >= 0; --t) {
+                const int64_t row = t * B + e;
+                const bool fresh = episode_starts[row] != 0;
+                const float* cp = t > 0 ? n.c + (row - B) * kHid : n.c0 + e * kHid;
+                const float* gt = n.gates + row * 4 * kHid;
+                for (int u = 0; u < kHid; ++u) {
+                    const float dh = n.d_h[row * kHid + u] + dhr[u];
+                    float d[4];
+                    const float dcn = cell_backward(gt[u], gt[kHid + u], gt[2 * kHid + u], gt[3 * kHid + u],
+                                                    n.c[row * kHid + u], fresh ? 0.0f : cp[u], dh, dc[u], d);
+                    dc[u] = fresh ? 0.0f : dcn;
+                    for (int g = 0; g < 4; ++g) dg[g * kHid + u] = d[g];
+                }
+                memcpy(n.d_gates + row * 4 * kHid, dg, kGates * sizeof(float));
+                if (t == 0) break;
+                for (int j = 0; j < kHid; ++j) {
+                    float acc = 0.0f;
+                    for (int u = 0; u < kGates; ++u) acc = fmaf(dg[u], n.w_hh[u * kHid + j], acc);
+                    dhr[j] = fresh ? 0.0f : acc;
+                }
+            }
+        }
+    }
     return HE_OK;
 }
 

@@ -1,0 +1,407 @@
+"""The RecurrentPPO update on the device: the LSTM over a stored sequence with per-step resets as a
+differentiable op (libhedgeactor's lstm_seq_fwd_kernel / lstm_seq_bwd_kernel, contract F1-F2 and
+B1-B4 of include/hedge_actor.h), sb3_contrib's evaluate_actions and RecurrentPPO.train's loss on
+top of it, in torch.
+
+    policy = RecurrentPolicy.from_sb3_zip("final_model.zip")
+    col = RolloutCollector(DeviceVecNormalize(venv), policy, gamma=0.98242, gae_lambda=0.91788, seed=7)
+    module = RecurrentPPOModule.from_policy(policy)
+    opt = torch.optim.Adam(module.parameters(), lr=1e-4, eps=1e-5)
+    while True:
+        buf = col.collect(256, buffer=buf)
+        stats = ppo_update(module, opt, buf, envs_per_batch=1024)
+        policy.load_state_dict(module.state_dict())
+
+Only the LSTM is a kernel: nn.LSTM has no per-step reset, so sb3_contrib's _process_sequence runs one
+LSTM call per time step, forward and again in autograd's backward.  Here a workgroup walks all L
+steps of its 32 envs inside one launch, actor and critic side by side.  The MLPs, the heads, the
+Gaussian log-probability, the loss and the optimizer are batched over L B rows and stay with torch.
+There is no torch fallback for the LSTM: a missing library is an error.
+"""
+import ctypes
+import io
+import zipfile
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+from .agent import ACT_DIM, HIDDEN, MLP, OBS_DIM, POLICY_KEYS, STATE_NAMES, _normalization, load
+
+_VP = ctypes.c_void_p
+NET_INPUTS = ("h0", "c0", "w_ih", "w_hh", "b_ih", "b_hh")   # lstm_sequence's per-network arguments
+
+
+class HaLstmSeqNet(ctypes.Structure):
+    _fields_ = [(k, _VP) for k in ("w_ih", "w_hh", "b_ih", "b_hh", "h0", "c0", "h", "c", "gates")]
+
+
+class HaLstmSeqBwd(ctypes.Structure):
+    _fields_ = [(k, _VP) for k in ("w_hh", "c0", "c", "gates", "d_h", "d_gates")]
+
+
+def _check(lib, status, what):
+    if status != _lib.HE_OK:
+        msg = (lib.ha_policy_last_error(None) or b"").decode()
+        if status in (_lib.HE_ESHAPE, _lib.HE_EINVAL):
+            raise ValueError(f"{what}: {msg}")
+        raise _lib.HedgeEnvError(f"{what} failed (status {status}): {msg}")
+
+
+def _f32(t, shape, name, device):
+    """t as a contiguous, 16-byte aligned float32 tensor of `shape` on `device` (no copy when it is)."""
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or t.device != device:
+        raise ValueError(f"{name} must be a float32 tensor of shape {tuple(shape)} on {device}, not "
+                         f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    t = t.detach().contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def _starts(es, L, B, device):
+    if es.dtype == torch.bool:
+        es = es.view(torch.uint8)
+    if es.dtype != torch.uint8 or tuple(es.shape) != (L, B) or es.device != device:
+        raise ValueError(f"episode_starts must be a uint8 / bool [{L}, {B}] tensor on {device}")
+    es = es.contiguous()
+    return es.clone() if es.data_ptr() % 16 else es
+
+
+def _stream(device):
+    from .vec_env import _raw_stream
+    return _raw_stream(device.index if device.index is not None else torch.cuda.current_device())
+
+
+def _workspace(lib, n, device):
+    return torch.empty(lib.ha_lstm_seq_workspace_bytes(n), dtype=torch.uint8, device=device)
+
+
+def lstm_seq_forward(x, episode_starts, nets, host=None):
+    """ha_lstm_seq_forward (ha_host_lstm_seq_forward with host=True; default: by x's device).
+    x [L,B,13] f32, episode_starts [L,B] u8 / bool, nets: one or two dicts of NET_INPUTS tensors ->
+    a list of (h [L,B,128], c [L,B,128], gates [L,B,4,128]) per network.  No autograd."""
+    lib = load()
+    dev = x.device
+    host = dev.type == "cpu" if host is None else bool(host)
+    if host != (dev.type == "cpu"):
+        raise ValueError("host=True takes CPU tensors, host=False tensors on a HIP device")
+    if x.dim() != 3 or x.shape[2] != OBS_DIM:
+        raise ValueError(f"x must be [L, B, {OBS_DIM}]")
+    L, B = int(x.shape[0]), int(x.shape[1])
+    x = _f32(x, (L, B, OBS_DIM), "x", dev)
+    es = _starts(episode_starts, L, B, dev)
+    n = len(nets)
+    arr = (HaLstmSeqNet * max(n, 1))()
+    keep, out = [x, es], []   # (keep: the aligned copies live until the call is enqueued)
+    shapes = dict(h0=(B, HIDDEN), c0=(B, HIDDEN), w_ih=(4 * HIDDEN, OBS_DIM), w_hh=(4 * HIDDEN, HIDDEN),
+                  b_ih=(4 * HIDDEN,), b_hh=(4 * HIDDEN,))
+    for k, net in enumerate(nets[:2]):
+        for name in NET_INPUTS:
+            t = _f32(net[name], shapes[name], name, dev)
+            keep.append(t)
+            setattr(arr[k], name, t.data_ptr())
+        h = torch.empty((L, B, HIDDEN), dtype=torch.float32, device=dev)
+        c = torch.empty((L, B, HIDDEN), dtype=torch.float32, device=dev)
+        gates = torch.empty((L, B, 4, HIDDEN), dtype=torch.float32, device=dev)
+        arr[k].h, arr[k].c, arr[k].gates = h.data_ptr(), c.data_ptr(), gates.data_ptr()
+        out.append((h, c, gates))
+    if host:
+        st = lib.ha_host_lstm_seq_forward(n, L, B, x.data_ptr(), es.data_ptr(), arr)
+    else:
+        with torch.cuda.device(dev):
+            ws = _workspace(lib, n, dev)
+            st = lib.ha_lstm_seq_forward(n, L, B, x.data_ptr(), es.data_ptr(), arr, ws.data_ptr(), _stream(dev))
+    _check(lib, st, "ha_lstm_seq_forward")
+    return out
+
+
+def lstm_seq_backward(episode_starts, nets, host=None):
+    """ha_lstm_seq_backward: nets = one or two dicts of w_hh [512,128], c0 [B,128], c [L,B,128], gates
+    [L,B,4,128], d_h [L,B,128] -> a list of d_gates [L,B,4,128] per network.  No autograd."""
+    lib = load()
+    first = nets[0]["d_h"]
+    dev = first.device
+    host = dev.type == "cpu" if host is None else bool(host)
+    if host != (dev.type == "cpu"):
+        raise ValueError("host=True takes CPU tensors, host=False tensors on a HIP device")
+    L, B = int(first.shape[0]), int(first.shape[1])
+    es = _starts(episode_starts, L, B, dev)
+    n = len(nets)
+    arr = (HaLstmSeqBwd * max(n, 1))()
+    shapes = dict(w_hh=(4 * HIDDEN, HIDDEN), c0=(B, HIDDEN), c=(L, B, HIDDEN), gates=(L, B, 4, HIDDEN),
+                  d_h=(L, B, HIDDEN))
+    keep, out = [es], []
+    for k, net in enumerate(nets[:2]):
+        for name, shape in shapes.items():
+            t = _f32(net[name], shape, name, dev)
+            keep.append(t)
+            setattr(arr[k], name, t.data_ptr())
+        dg = torch.empty((L, B, 4, HIDDEN), dtype=torch.float32, device=dev)
+        arr[k].d_gates = dg.data_ptr()
+        out.append(dg)
+    if host:
+        st = lib.ha_host_lstm_seq_backward(n, L, B, es.data_ptr(), arr)
+    else:
+        with torch.cuda.device(dev):
+            ws = _workspace(lib, n, dev)
+            st = lib.ha_lstm_seq_backward(n, L, B, es.data_ptr(), arr, ws.data_ptr(), _stream(dev))
+    _check(lib, st, "ha_lstm_seq_backward")
+    return out
+
+
+def weight_grads(d_gates, x, h, h0, episode_starts, rows=1 << 18, block=128):
+    """The LSTM's weight gradients from d_gates [L,B,4,128], as f64 tensors: dW_ih = d_gates^T x,
+    dW_hh = d_gates^T h_prev, db_ih = db_hh = sum d_gates, with h_prev = h shifted by one step, h0 in
+    front, zeroed where episode_starts.  The sums run over L B rows: one batched f32 GEMM against
+    [x | h_prev] sums blocks of `block` rows, and the blocks' results are added in f64 (about `rows`
+    rows a pass).  One f32 GEMM over all rows misses the tests' 4 x d_ref bound by its own rounding,
+    f64 GEMMs of these shapes are 30 x slower."""
+    L, B = d_gates.shape[:2]
+    f64, G, K = torch.float64, 4 * HIDDEN, OBS_DIM + HIDDEN
+    steps = max(1, rows // B)
+    w = torch.zeros((G, K), dtype=f64, device=d_gates.device)
+    b = torch.zeros(G, dtype=f64, device=d_gates.device)
+    for t0 in range(0, L, steps):
+        t1 = min(t0 + steps, L)
+        n = (t1 - t0) * B
+        dg = d_gates[t0:t1].reshape(n, G)
+        first = (h0 if t0 == 0 else h[t0 - 1]).unsqueeze(0)
+        keep = (episode_starts[t0:t1] == 0).to(h.dtype).unsqueeze(-1)
+        xh = torch.cat([x[t0:t1], torch.cat([first, h[t0:t1 - 1]], 0) * keep], -1).reshape(n, K)
+        nb = n // block
+        if nb:
+            d3 = dg[:nb * block].view(nb, block, G)
+            w += torch.bmm(d3.transpose(1, 2), xh[:nb * block].view(nb, block, K)).sum(0, dtype=f64)
+            b += d3.sum(1).sum(0, dtype=f64)
+        if n > nb * block:
+            w += (dg[nb * block:].t() @ xh[nb * block:]).to(f64)
+            b += dg[nb * block:].sum(0).to(f64)
+    return w[:, :OBS_DIM], w[:, OBS_DIM:], b, b.clone()
+
+
+class _LstmSeq(torch.autograd.Function):
+    """h of one or two networks over the same x and episode_starts; per network the six NET_INPUTS."""
+
+    @staticmethod
+    def forward(ctx, host, x, episode_starts, *tensors):
+        n = len(tensors) // len(NET_INPUTS)
+        nets = [dict(zip(NET_INPUTS, tensors[6 * k:6 * k + 6])) for k in range(n)]
+        out = lstm_seq_forward(x, episode_starts, nets, host=host)
+        saved = [x, episode_starts]
+        for net, (h, c, gates) in zip(nets, out):
+            saved += [net["h0"], net["c0"], net["w_hh"], h, c, gates]
+        ctx.save_for_backward(*saved)
+        ctx.host, ctx.n = host, n
+        return tuple(h for h, _, _ in out)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *d_h):
+        x, es = ctx.saved_tensors[:2]
+        per = [ctx.saved_tensors[2 + 6 * k:8 + 6 * k] for k in range(ctx.n)]
+        nets = []
+        for (h0, c0, w_hh, h, c, gates), d in zip(per, d_h):
+            d = torch.zeros_like(h) if d is None else d
+            nets.append(dict(w_hh=w_hh, c0=c0, c=c, gates=gates, d_h=d))
+        d_gates = lstm_seq_backward(es, nets, host=ctx.host)
+        grads = [None, None, None]
+        for (h0, c0, w_hh, h, c, gates), dg in zip(per, d_gates):
+            grads += [None, None, *(g.to(torch.float32) for g in weight_grads(dg, x, h, h0, es))]
+        return tuple(grads)
+
+
+def lstm_sequence(x, episode_starts, h0, c0, w_ih, w_hh, b_ih, b_hh, host=None):
+    """The LSTM (13 -> 128, one layer, torch's gate order) over x [L,B,13] from (h0, c0) [B,128], the
+    state zeroed before every step where episode_starts [L,B] is set -> h [L,B,128], differentiable
+    in the four weight tensors.  x, h0 and c0 receive no gradient (SB3 stores them as constants).
+    One forward and one backward launch; host=True (default for CPU tensors) runs the host build."""
+    host = x.device.type == "cpu" if host is None else bool(host)
+    return _LstmSeq.apply(host, x, episode_starts, h0, c0, w_ih, w_hh, b_ih, b_hh)[0]
+
+
+def lstm_sequence_pair(x, episode_starts, actor, critic, host=None):
+    """lstm_sequence for actor and critic in one launch each way: `actor`, `critic` are the NET_INPUTS
+    tuples (h0, c0, w_ih, w_hh, b_ih, b_hh) -> (h_pi, h_vf)."""
+    host = x.device.type == "cpu" if host is None else bool(host)
+    return _LstmSeq.apply(host, x, episode_starts, *actor, *critic)
+
+
+# --------------------------------------------------------------------------- the policy as a torch module
+class _Lstm(torch.nn.Module):
+    """The four tensors of a one-layer nn.LSTM under nn.LSTM's names (a container: the op is lstm_sequence)."""
+
+    def __init__(self):
+        super().__init__()
+        P = torch.nn.Parameter
+        self.weight_ih_l0 = P(torch.zeros(4 * HIDDEN, OBS_DIM))
+        self.weight_hh_l0 = P(torch.zeros(4 * HIDDEN, HIDDEN))
+        self.bias_ih_l0 = P(torch.zeros(4 * HIDDEN))
+        self.bias_hh_l0 = P(torch.zeros(4 * HIDDEN))
+
+    def tensors(self):
+        return self.weight_ih_l0, self.weight_hh_l0, self.bias_ih_l0, self.bias_hh_l0
+
+
+class _MlpExtractor(torch.nn.Module):
+    def __init__(self, act):
+        super().__init__()
+        L = torch.nn.Linear
+        self.policy_net = torch.nn.Sequential(L(HIDDEN, MLP), act(), L(MLP, MLP), act())
+        self.value_net = torch.nn.Sequential(L(HIDDEN, MLP), act(), L(MLP, MLP), act())
+
+
+class RecurrentPPOModule(torch.nn.Module):
+    """sb3_contrib's RecurrentActorCriticPolicy (MlpLstmPolicy: lstm_actor and lstm_critic 13 -> 128,
+    net_arch 64-64, a state-independent log_std) with its 21 tensors under the checkpoint's own names:
+    state_dict() feeds RecurrentPolicy.load_state_dict as it is.  activation: "tanh" (SB3's default)
+    or "relu".  obs_mean / obs_var: the statistics a RecurrentPolicy applies to raw obs (contract step
+    2); leave them out when the buffer holds normalised obs (a DeviceVecNormalize env)."""
+
+    def __init__(self, activation="tanh", obs_mean=None, obs_var=None, clip_obs=10.0, epsilon=1e-8):
+        super().__init__()
+        acts = {"tanh": torch.nn.Tanh, "relu": torch.nn.ReLU}
+        if activation not in acts:
+            raise ValueError(f"activation must be one of {sorted(acts)}, not {activation!r}")
+        if (obs_mean is None) != (obs_var is None):
+            raise ValueError("obs_mean and obs_var come together")
+        self.activation = activation
+        self.lstm_actor, self.lstm_critic = _Lstm(), _Lstm()
+        self.mlp_extractor = _MlpExtractor(acts[activation])
+        self.action_net = torch.nn.Linear(MLP, ACT_DIM)
+        self.value_net = torch.nn.Linear(MLP, 1)
+        self.log_std = torch.nn.Parameter(torch.zeros(ACT_DIM))
+        self.clip_obs, self.epsilon = clip_obs, float(epsilon)
+        if obs_mean is not None:
+            for name, v in (("obs_mean", obs_mean), ("obs_var", obs_var)):
+                t = torch.as_tensor(v, dtype=torch.float64).reshape(-1).clone()
+                if t.numel() != OBS_DIM:
+                    raise ValueError(f"{name} has {t.numel()} entries, the obs has {OBS_DIM}")
+                self.register_buffer(name, t, persistent=False)
+        else:
+            self.obs_mean = self.obs_var = None
+
+    # ------------------------------------------------------------------ loaders
+    @classmethod
+    def from_state_dict(cls, sd, normalization=None, device=None, **kw):
+        mean, var, over = _normalization(normalization)
+        m = cls(obs_mean=mean, obs_var=var, **dict(over, **kw))
+        m.load_state_dict({k: torch.as_tensor(sd[k]).to(torch.float32) for k, _, _ in POLICY_KEYS})
+        return m if device is None else m.to(device)
+
+    @classmethod
+    def from_sb3_zip(cls, path, normalization=None, **kw):
+        """An SB3 `model.save()` zip: its policy.pth is a plain torch state dict."""
+        with zipfile.ZipFile(path) as z:
+            sd = torch.load(io.BytesIO(z.read("policy.pth")), map_location="cpu", weights_only=True)
+        return cls.from_state_dict(sd, normalization=normalization, **kw)
+
+    @classmethod
+    def from_policy(cls, policy, device=None):
+        """The tensors, activation and statistics of an agent.RecurrentPolicy, on its device."""
+        a = policy._arrays
+        m = cls(activation=policy.activation, obs_mean=a.get("obs_mean"), obs_var=a.get("obs_var"),
+                clip_obs=policy.clip_obs, epsilon=policy.epsilon)
+        m.load_state_dict({k: torch.from_numpy(a[f].copy()) for k, f, _ in POLICY_KEYS})
+        return m.to(policy.device_name if device is None else device)
+
+    # ------------------------------------------------------------------ evaluate_actions
+    def normalize_obs(self, obs):
+        """Contract step 2 in torch f64: f32(clip((f64(obs) - mean) / sqrt(var + epsilon), +-clip))."""
+        if self.obs_mean is None:
+            return obs
+        q = (obs.to(torch.float64) - self.obs_mean) / torch.sqrt(self.obs_var + self.epsilon)
+        if self.clip_obs is not None:
+            q = torch.clamp(q, -float(self.clip_obs), float(self.clip_obs))
+        return q.to(torch.float32)
+
+    def heads(self, h_pi, h_vf, actions):
+        """The part after the LSTMs: values, log_prob, entropy of `actions` (trailing shapes [] each)."""
+        mean = self.action_net(self.mlp_extractor.policy_net(h_pi))
+        values = self.value_net(self.mlp_extractor.value_net(h_vf)).squeeze(-1)
+        dist = torch.distributions.Normal(mean, torch.ones_like(mean) * self.log_std.exp())
+        return values, dist.log_prob(actions).sum(-1), dist.entropy().sum(-1)
+
+    def evaluate_actions(self, obs, actions, episode_starts, states0, host=None):
+        """sb3_contrib's evaluate_actions over whole sequences: obs [L,B,13], actions [L,B,2],
+        episode_starts [L,B], states0 = (h_pi, c_pi, h_vf, c_vf) [B,128] before step 0 ->
+        (values, log_prob, entropy), each [L,B]."""
+        x = self.normalize_obs(obs)
+        h_pi, h_vf = lstm_sequence_pair(x, episode_starts, (states0[0], states0[1], *self.lstm_actor.tensors()),
+                                        (states0[2], states0[3], *self.lstm_critic.tensors()), host=host)
+        return self.heads(h_pi, h_vf, actions)
+
+
+# --------------------------------------------------------------------------- the update
+def ppo_loss(values, log_prob, entropy, old_log_prob, advantages, returns, clip_range, ent_coef, vf_coef,
+             normalize_advantage=True):
+    """sb3_contrib 2.6.0 RecurrentPPO.train's loss for one minibatch without padding (mask all ones,
+    clip_range_vf None) -> (loss, stats)."""
+    adv = advantages
+    if normalize_advantage:
+        adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+    ratio = torch.exp(log_prob - old_log_prob)
+    policy_loss = -torch.min(adv * ratio, adv * torch.clamp(ratio, 1 - clip_range, 1 + clip_range)).mean()
+    value_loss = ((returns - values) ** 2).mean()
+    entropy_loss = -entropy.mean()
+    loss = policy_loss + ent_coef * entropy_loss + vf_coef * value_loss
+    with torch.no_grad():
+        log_ratio = log_prob - old_log_prob
+        stats = dict(loss=loss.detach(), policy_gradient_loss=policy_loss.detach(), value_loss=value_loss.detach(),
+                     entropy_loss=entropy_loss.detach(), approx_kl=((torch.exp(log_ratio) - 1) - log_ratio).mean(),
+                     clip_fraction=(torch.abs(ratio - 1) > clip_range).float().mean())
+    return loss, stats
+
+
+def minibatch(buffer, idx, k0, k1):
+    """Envs `idx` (an int64 tensor) x steps [k0, k1) of a RolloutBuffer -> a dict of contiguous tensors
+    and states0, the LSTM states before step k0."""
+    sl = slice(k0, k1)
+    mb = {name: getattr(buffer, name)[sl].index_select(1, idx)
+          for name in ("observations", "actions", "episode_starts", "log_probs", "advantages", "returns")}
+    if k0 == 0:
+        mb["states0"] = tuple(getattr(buffer, s).index_select(0, idx) for s in STATE_NAMES)
+    else:
+        st = buffer.states[k0].index_select(0, idx)
+        mb["states0"] = tuple(st[:, i].contiguous() for i in range(4))
+    return mb
+
+
+def ppo_update(module, optimizer, buffer, *, n_epochs=10, envs_per_batch=None, window=None, clip_range=0.3,
+               ent_coef=1e-5, vf_coef=0.5, max_grad_norm=0.5, normalize_advantage=True, generator=None):
+    """RecurrentPPO.train over a collect.RolloutBuffer: n_epochs passes, each over a fresh permutation
+    of the envs (from `generator`, a torch.Generator on the buffer's device) cut into groups of
+    envs_per_batch (default: all), each group x each time window one optimizer step.  window=None: the
+    whole K steps from buffer.h_pi ...; window=W (dividing K): W steps from buffer.states[k0], which
+    collect(states=True) stores.  Defaults: the reference's default_hpo_params (train_ppo_v2.py:601-605:
+    clip_range 0.3, ent_coef 1e-5, vf_coef 0.5, max_grad_norm 0.5, n_epochs 10).  Nothing synchronises
+    with the host; returns the last minibatch's statistics and the mean loss as device scalars."""
+    K, n = buffer.k_steps, buffer.n_envs
+    W = K if window is None else int(window)
+    if W < 1 or K % W:
+        raise ValueError(f"window = {window} must divide the buffer's {K} steps")
+    if W != K and buffer.states is None:
+        raise ValueError("window < K starts from the states of step k0: collect the buffer with states=True")
+    per = n if envs_per_batch is None else int(envs_per_batch)
+    if per < 1:
+        raise ValueError("envs_per_batch must be >= 1")
+    dev = buffer.observations.device
+    params = [p for p in module.parameters() if p.requires_grad]
+    stats, total, count = {}, None, 0
+    for _ in range(int(n_epochs)):
+        perm = torch.randperm(n, device=dev, generator=generator)
+        for lo in range(0, n, per):
+            idx = perm[lo:lo + per]
+            for k0 in range(0, K, W):
+                mb = minibatch(buffer, idx, k0, k0 + W)
+                values, log_prob, entropy = module.evaluate_actions(mb["observations"], mb["actions"],
+                                                                    mb["episode_starts"], mb["states0"])
+                loss, stats = ppo_loss(values, log_prob, entropy, mb["log_probs"], mb["advantages"], mb["returns"],
+                                       clip_range, ent_coef, vf_coef, normalize_advantage)
+                optimizer.zero_grad(set_to_none=True)
+                loss.backward()
+                stats["grad_norm"] = torch.nn.utils.clip_grad_norm_(params, max_grad_norm)
+                optimizer.step()
+                total = stats["loss"] if total is None else total + stats["loss"]
+                count += 1
+    if count:
+        stats["mean_loss"] = total / count
+    return stats

@@ -3,7 +3,8 @@
  * (sb3_contrib RecurrentActorCriticPolicy: obs 13 -> LSTM 128 -> Linear 64 -> Linear 64 ->
  * Linear 2) evaluated for N device-resident envs in one HIP kernel on MI355X (gfx950), the
  * per-episode sums of a closed-loop evaluation around he_step, and the training side: actor,
- * critic, action sampling and log-probability of a rollout step in one launch, and GAE.
+ * critic, action sampling and log-probability of a rollout step in one launch, GAE, and for the
+ * PPO update both LSTMs over a stored sequence with per-step resets, forward and backward.
  *
  * Conventions (as hedge_env.h): plain C types, every entry point returns an ha_status (the
  * he_status values), the last failure's message is ha_last_error(handle), no C++ exception
@@ -56,6 +57,33 @@
  *         advantages[k] = last; returns[k] = last + values[k]
  *       The env never truncates an episode (it ends by `terminated` only), so SB3's time-out
  *       bootstrap (reward += gamma V(terminal_obs)) has no counterpart here.
+ *
+ * The LSTM over a stored sequence, forward and backward (ha_lstm_seq_forward / _backward: what
+ * sb3_contrib's _process_sequence computes inside evaluate_actions, one LSTM call per time step
+ * with the state zeroed at episode_starts, and autograd's backward of it; restated).  Arrays are
+ * laid out [L][B][...] (SB3's (buffer_size, n_envs, ...)); per env e and network:
+ *   F1. the state before step 0 is (h0[e], c0[e]); for t = 0 .. L-1 steps 1, 3 and 4 above with
+ *       x = x[t][e] (already normalised) and episode_start = episode_starts[t][e]: the reset, the
+ *       142-term k-ordered fmaf gate chains from b_ih + b_hh, cell_update.  h[t], c[t] are the
+ *       state after step t: for the same tensors and inputs the bits that t + 1 successive
+ *       ha_policy_step / ha_host_policy_step calls leave in h_pi, c_pi (h_vf, c_vf).
+ *   F2. gates[t][e][0..3][u] = the post-activation i, f, g, o of unit u at step t (f32), the
+ *       values step 4 forms on its way to c' and h'.
+ *   B1. the carries dh_rec[128] and dc[128] start at 0; t runs from L-1 down to 0.  h0, c0 and x
+ *       receive no gradient (SB3 stores the states of a rollout as constants).
+ *   B2. per unit u, with (i, f, g, o) = gates[t], c_prev = 0 where episode_starts[t], else
+ *       c[t-1] (c0 at t = 0), and tc = f32(tanh_f64(c[t])); every operation one f32 rounding, the
+ *       products in the order written, no contraction:
+ *         dh  = d_h[t] + dh_rec
+ *         dct = ((dh o) (1 - tc tc)) + dc
+ *         d_gates[t] = { (dct g) (i (1 - i)), (dct c_prev) (f (1 - f)), (dct i) (1 - g g),
+ *                        (dh tc) (o (1 - o)) }
+ *   B3. dc = episode_starts[t] ? 0 : dct f.
+ *   B4. dh_rec[j] = episode_starts[t] ? 0 : the k-ordered f32 fmaf chain from 0 over
+ *       u = 0 .. 511 (torch's gate rows: i, f, g, o blocks of 128) of d_gates[t][u] w_hh[u][j].
+ *       v_mfma_f32_32x32x2_f32 over K = 512 in one accumulator computes exactly this chain.
+ *   The weight gradients are sums over the L B rows of d_gates (dW_ih = d_gates^T x,
+ *   dW_hh = d_gates^T h_prev, db_ih = db_hh = sum d_gates): GEMMs, left to the caller.
  */
 #ifndef HEDGE_ACTOR_H
 #define HEDGE_ACTOR_H
@@ -231,6 +259,58 @@ ha_status ha_host_policy_step(const ha_policy_weights* w, int64_t n, int64_t env
 ha_status ha_host_gae(int64_t n, int64_t K, double gamma, double gae_lambda, const float* rewards,
                       const float* values, const uint8_t* episode_starts, const float* last_values,
                       const uint8_t* last_dones, float* advantages, float* returns);
+
+/* ---- the LSTM over a stored sequence with per-step resets, forward and backward (F1-F2, B1-B4) ---- */
+
+/* One network of ha_lstm_seq_forward.  The weights are read in torch layout as they stand when
+ * the call runs on the stream (an optimizer step changes them in place): w_ih [512][13], w_hh
+ * [512][128], b_ih, b_hh [512]; h0, c0 [B][128] in; h, c [L][B][128] and gates [L][B][4][128] out. */
+typedef struct ha_lstm_seq_net {
+    const float* w_ih;
+    const float* w_hh;
+    const float* b_ih;
+    const float* b_hh;
+    const float* h0;
+    const float* c0;
+    float* h;
+    float* c;
+    float* gates;
+} ha_lstm_seq_net;
+
+/* One network of ha_lstm_seq_backward: w_hh [512][128], c0 [B][128], the forward's c [L][B][128]
+ * and gates [L][B][4][128], d_h [L][B][128] (the loss's gradient of every h[t]) in; d_gates
+ * [L][B][4][128] out (the gradient of the pre-activations, rows in torch's order i, f, g, o). */
+typedef struct ha_lstm_seq_bwd {
+    const float* w_hh;
+    const float* c0;
+    const float* c;
+    const float* gates;
+    const float* d_h;
+    float* d_gates;
+} ha_lstm_seq_bwd;
+
+/* Bytes of the workspace both calls take for n_nets (1 or 2) networks, 0 for any other count:
+ * the weights packed in the kernels' fragment order.  Each call packs what it reads from the
+ * tensors it is given (one small launch before the sequence kernel), so the workspace carries
+ * nothing from call to call and one workspace serves forward and backward in stream order. */
+size_t ha_lstm_seq_workspace_bytes(int64_t n_nets);
+
+/* n_nets = 1 or 2 networks (`nets` is a HOST array of structs holding DEVICE pointers) over the
+ * same x [L][B][13] and episode_starts [L][B] u8: one launch over a grid of (tiles of 32 envs,
+ * n_nets), each workgroup walking all L steps of its tile.  Every pointer is a DEVICE pointer,
+ * 16-byte aligned; stream-ordered, no host synchronisation, no allocation.  n_nets other than 1
+ * or 2, L or B < 1 or B > 2^30 is HE_ESHAPE; a NULL or misaligned pointer HE_EINVAL; the message
+ * is ha_policy_last_error(NULL). */
+ha_status ha_lstm_seq_forward(int64_t n_nets, int64_t L, int64_t B, const float* x, const uint8_t* episode_starts,
+                              const ha_lstm_seq_net* nets, void* workspace, void* stream);
+ha_status ha_lstm_seq_backward(int64_t n_nets, int64_t L, int64_t B, const uint8_t* episode_starts,
+                               const ha_lstm_seq_bwd* nets, void* workspace, void* stream);
+
+/* The same arithmetic on the host, HOST pointers (no alignment asked), no workspace. */
+ha_status ha_host_lstm_seq_forward(int64_t n_nets, int64_t L, int64_t B, const float* x,
+                                   const uint8_t* episode_starts, const ha_lstm_seq_net* nets);
+ha_status ha_host_lstm_seq_backward(int64_t n_nets, int64_t L, int64_t B, const uint8_t* episode_starts,
+                                    const ha_lstm_seq_bwd* nets);
 
 #ifdef __cplusplus
 }

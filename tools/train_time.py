@@ -1,0 +1,133 @@
+"""Device time of the RecurrentPPO update's LSTM (cantorrl_amd.train): lstm_sequence_pair forward plus
+backward (two launches each way: the packing kernel and the sequence kernel, then the weight-gradient
+GEMMs) against -- same box, same process -- the all-torch composition of the same op: sb3_contrib's
+_process_sequence loop of one cell per time step with the state zeroed at episode starts, under
+autograd, f32.  And one ppo_update epoch over a buffer of the first shape.  HIP events around each
+call, warm-up first, the median.
+
+    python tools/train_time.py [--reps R] [--out FILE.jsonl] [--shapes L,B ...]
+
+Default shapes: L = 256 with B = 4,096 and 16,384 (the largest power of two at which the all-torch
+composition's saved activations, about 8 KB per step, env and network, still fit beside the kernel's
+3 KB), and L = 32, B = 2 (the reference's BATCH_SIZE_AGENT = 32 steps of N_ENVS = 2).  One JSON line
+per shape; with --out they are appended to the file as well (profiles/train_time_*.jsonl).
+FLOP per env-step and network: 2 x 512 x 141 forward, 2 x 512 x 128 backward.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from actor_time import median_us  # noqa: E402
+from cantorrl_amd import train  # noqa: E402
+from cantorrl_amd.agent import POLICY_KEYS  # noqa: E402
+from cantorrl_amd.collect import RolloutBuffer  # noqa: E402
+
+FLOP_FWD, FLOP_BWD = 2 * 512 * 141, 2 * 512 * 128
+DEV = "cuda:0"
+
+
+def torch_lstm_loop(x, es, h0, c0, w_ih, w_hh, b_ih, b_hh):
+    h, c = h0, c0
+    hs = []
+    for t in range(x.shape[0]):
+        keep = (es[t] == 0).to(x.dtype).unsqueeze(-1)
+        h, c = h * keep, c * keep
+        i, f, g, o = (x[t] @ w_ih.t() + b_ih + h @ w_hh.t() + b_hh).chunk(4, -1)
+        c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+        h = torch.sigmoid(o) * torch.tanh(c)
+        hs.append(h)
+    return torch.stack(hs)
+
+
+def module(rng):
+    m = train.RecurrentPPOModule()
+    m.load_state_dict({k: torch.from_numpy((rng.uniform(-1, 1, shape) / np.sqrt(shape[-1])).astype(np.float32))
+                       for k, _, shape in POLICY_KEYS})
+    return m.to(DEV)
+
+
+def measure(L, B, reps):
+    rng = np.random.default_rng(0)
+    m = module(rng)
+    g = torch.Generator(device=DEV).manual_seed(1)
+    x = torch.rand((L, B, 13), device=DEV, generator=g) * 4 - 2
+    es = (torch.rand((L, B), device=DEV, generator=g) < 0.004).to(torch.uint8)
+    st = [torch.rand((B, 128), device=DEV, generator=g) - 0.5 for _ in range(4)]
+    d_h = [torch.randn((L, B, 128), device=DEV, generator=g) for _ in range(2)]
+    nets = ((st[0], st[1], *m.lstm_actor.tensors()), (st[2], st[3], *m.lstm_critic.tensors()))
+
+    def kernel_fwd():
+        with torch.no_grad():
+            train.lstm_sequence_pair(x, es, *nets)
+
+    def kernel_both():
+        m.zero_grad(set_to_none=True)
+        h = train.lstm_sequence_pair(x, es, *nets)
+        torch.autograd.backward(h, d_h)
+
+    def torch_fwd():
+        with torch.no_grad():
+            for n in nets:
+                torch_lstm_loop(x, es, *n)
+
+    def torch_both():
+        m.zero_grad(set_to_none=True)
+        h = [torch_lstm_loop(x, es, *n) for n in nets]
+        torch.autograd.backward(h, d_h)
+
+    r = dict(L=L, B=B, reps=reps, device=torch.cuda.get_device_name(0))
+    r["kernel_fwd_us"] = round(median_us(kernel_fwd, reps, 3), 1)
+    r["kernel_fwd_bwd_us"] = round(median_us(kernel_both, reps, 3), 1)
+    treps = reps if L * B <= 2 ** 20 else max(reps // 10, 3)   # the loop is 256 x ~40 launches a pass
+    r["torch_fwd_us"] = round(median_us(torch_fwd, treps, 2), 1)
+    r["torch_fwd_bwd_us"] = round(median_us(torch_both, treps, 2), 1)
+    r["torch_reps"] = treps
+    r["speedup_fwd_bwd"] = round(r["torch_fwd_bwd_us"] / r["kernel_fwd_bwd_us"], 2)
+    r["kernel_fwd_tflops"] = round(2 * L * B * FLOP_FWD / r["kernel_fwd_us"] / 1e6, 2)
+    r["kernel_us_per_step_fwd"] = round(r["kernel_fwd_us"] / L, 2)
+    r["kernel_us_per_step_bwd"] = round((r["kernel_fwd_bwd_us"] - r["kernel_fwd_us"]) / L, 2)
+    return r, m
+
+
+def measure_update(m, K, n, per, reps):
+    buf = RolloutBuffer(K, n, DEV)
+    g = torch.Generator(device=DEV).manual_seed(2)
+    for name in ("observations", "actions", "rewards", "values", "advantages", "returns", "h_pi", "c_pi", "h_vf", "c_vf"):
+        t = getattr(buf, name)
+        t.copy_(torch.randn(t.shape, device=DEV, generator=g) * 0.5)
+    buf.log_probs.fill_(-1.0)
+    buf.episode_starts.copy_((torch.rand((K, n), device=DEV, generator=g) < 0.004).to(torch.uint8))
+    opt = torch.optim.Adam(m.parameters(), lr=1e-5, eps=1e-5)
+    us = median_us(lambda: train.ppo_update(m, opt, buf, n_epochs=1, envs_per_batch=per), reps, 1)
+    return dict(ppo_update_epoch_us=round(us, 1), K=K, n_envs=n, envs_per_batch=per, minibatches=-(-n // per), update_reps=reps)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", nargs="*", default=["256,4096", "256,16384", "32,2"])
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    lines = []
+    for k, s in enumerate(a.shapes):
+        L, B = (int(v) for v in s.split(","))
+        r, m = measure(L, B, a.reps)
+        if k == 0:
+            r.update(measure_update(m, L, B, max(B // 4, 1), max(a.reps // 5, 3)))
+        del m
+        torch.cuda.empty_cache()
+        lines.append(json.dumps(r))
+        print(lines[-1], flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
