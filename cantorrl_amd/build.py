@@ -10,6 +10,7 @@ Flags that matter for parity with the NumPy reference:
   -fhip-fp32-correctly-rounded-divide-sqrt  IEEE f32 '/' and sqrtf
   -fno-gpu-flush-denormals-to-zero        keep f32 denormals
 """
+import glob
 import os
 import subprocess
 import sys
@@ -17,7 +18,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc", "hedge_env.hip")
-DEPS = [SRC, os.path.join(HERE, "csrc", "he_math.h"), os.path.join(REPO, "include", "hedge_env.h")]
+# Every library depends on every header of the tree.  This over-rebuilds by design (a touched
+# ha_math.h also rebuilds libhedgeenv): no per-library list can then miss a new header.
+HEADERS = sorted(glob.glob(os.path.join(HERE, "csrc", "*.h")) + glob.glob(os.path.join(REPO, "include", "*.h")))
 OUT = os.path.join(HERE, "lib", "libhedgeenv.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("CANTORRL_ARCH", "gfx950")
@@ -38,15 +41,14 @@ ENV_FLAGS = ["-mllvm", "-disable-machine-licm", "-mllvm", "-phi-node-folding-thr
 
 
 RB_SRC = os.path.join(HERE, "csrc", "rbergomi.hip")
-RB_DEPS = [RB_SRC, os.path.join(HERE, "csrc", "he_math.h"), os.path.join(REPO, "include", "rbergomi.h")]
+RB_DEPS = [RB_SRC] + HEADERS
 RB_OUT = os.path.join(HERE, "lib", "librbergomi.so")
 VN_SRC = os.path.join(HERE, "csrc", "vecnorm.hip")
 AN_SRC = os.path.join(HERE, "csrc", "analytics.hip")
-DEPS = DEPS + [VN_SRC, AN_SRC, os.path.join(HERE, "csrc", "vn_moments.h"), os.path.join(HERE, "csrc", "vn_sb3.h")]
+DEPS = [SRC, VN_SRC, AN_SRC] + HEADERS
 # the RecurrentPPO actor (include/hedge_actor.h): its own library, the plain FLAGS
 HA_SRC = os.path.join(HERE, "csrc", "hedge_actor.hip")
-HA_DEPS = [HA_SRC, os.path.join(HERE, "csrc", "ha_math.h"), os.path.join(HERE, "csrc", "he_math.h"),
-           os.path.join(REPO, "include", "hedge_actor.h"), os.path.join(REPO, "include", "hedge_env.h")]
+HA_DEPS = [HA_SRC] + HEADERS
 HA_OUT = os.path.join(HERE, "lib", "libhedgeactor.so")
 TARGETS = [([SRC, VN_SRC, AN_SRC], DEPS, OUT, ENV_FLAGS), ([RB_SRC], RB_DEPS, RB_OUT, []),
            ([HA_SRC], HA_DEPS, HA_OUT, [])]

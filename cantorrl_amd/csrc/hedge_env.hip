@@ -715,9 +715,6 @@ __device__ __forceinline__ double mills_u(double u) {
     return r;
 }
 __device__ __forceinline__ double mills(double a) {
-#if HE_BOOK_DIAG == 1
-    return a * 0.25;  // diagnostic builds only (tools/gpu): the book without its tails
-#endif
     const double d = a + kMillsC;                        // in [3.5, 41]: no special cases
     // v_rcp_f64 is within 4.7e-8 of 1 / d on [3.5, 43], one Newton step within 2.3e-15
     // (tools/probe/rcp_f64.hip, profiles/r04s3_rcp_f64.txt): u = A - B y then carries
@@ -734,10 +731,6 @@ __device__ __forceinline__ double mills(double a) {
 // they spilled the Heston producers' registers)
 template <bool SEQ = false>
 __device__ __forceinline__ void mills2(double a1, double a2, double* r1, double* r2) {
-#if HE_BOOK_DIAG == 1
-    *r1 = mills(a1);
-    *r2 = mills(a2);
-#else
     const double d1 = a1 + kMillsC, d2 = a2 + kMillsC;
     const double P = d1 * d2;
     double Y = __builtin_amdgcn_rcp(P);
@@ -746,7 +739,6 @@ __device__ __forceinline__ void mills2(double a1, double a2, double* r1, double*
     *r1 = mills_u(fma(-kMillsB, d2 * Y, kMillsA));
     if (SEQ) __builtin_amdgcn_sched_barrier(0);
     *r2 = mills_u(u2);
-#endif
 }
 
 // |d| clamped to the range of the fit, and its phi
@@ -940,9 +932,6 @@ __device__ __forceinline__ double book_value(const Params& p, double S, double v
         b.lam = fma(p.r_d, y * y, 0.5);
     }
     double B = 0.0;
-#if HE_BOOK_DIAG == 2
-    return S * 1e-3;  // diagnostic builds only: no book pricing at all
-#endif
     for (int k = 0; k < p.book_n; ++k) {
         BookOpt o;
         if (opts) {  // an LDS copy: the type and expiry back in SGPRs (uniform branches)
@@ -2450,10 +2439,6 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
     auto run_blk = [&](auto&& step, auto&& pre_ok) {
         LDS_BAR();  // block 0 produced
         for (int b = 0; b < nfull; ++b) {
-#if defined(HE_LDS_DIAG) && HE_LDS_DIAG == 2
-            LDS_BAR();  // diagnostic build: the steppers only keep the barrier count
-            continue;
-#endif
             const int buf = b % NB;
             auto slots = [&](auto plain) {
 #pragma unroll
@@ -2485,14 +2470,12 @@ __device__ __forceinline__ void lds_stepper(const Params& p, State s, const Io& 
             LDS_BAR();  // buffer b % NB handed back, block b + 1 produced
         }
         if (tail) {
-#if !(defined(HE_LDS_DIAG) && HE_LDS_DIAG == 2)
             const int buf = nfull % NB;
             for (int sl = 0; sl < tail; ++sl) {
                 const int k = nfull * kLdsM + sl;
                 step(buf, sl, k, POL ? make_float2(0.0f, 0.0f) : ld2(gact, (int64_t)k * N + i), std::false_type{},
                      std::false_type{});
             }
-#endif
             LDS_BAR();
         }
     };
@@ -2887,10 +2870,6 @@ __device__ __forceinline__ void lds_producer(const Params& p, int k_steps, const
     constexpr bool kTame = TAME_OK && PLAIN_OK && LEAN && !HESTON && !BOOK && kLdsLanes == 2;
     LDS_T0();
     for (int bp = 0; bp <= nb; ++bp) {
-#if defined(HE_LDS_DIAG) && HE_LDS_DIAG == 1
-        LDS_BAR();  // diagnostic build: the producers only keep the barrier count
-        continue;
-#endif
         if (bp < nb) {
             const int kb = bp * kLdsM;
             const int len = (k_steps - kb) < kLdsM ? (k_steps - kb) : kLdsM;
@@ -3483,11 +3462,7 @@ __device__ __forceinline__ void lds_replay_loader(const Params& p, State s, int 
                 // marks), the slots after it the new path's rows 1, 2, ...
                 const int sl = sl0 + h;
                 const int64_t r = (sl <= rsl) ? ro + sl : rn + (sl - rsl);
-#if defined(HE_REPLAY_DIAG) && HE_REPLAY_DIAG == 1
-                A[h] = make_float4(100.0f + (float)sl, 0.04f, 3.0f, 2.5f);  // diagnostic build: no table reads
-#else
                 A[h] = ld4(rec, r);
-#endif
             }
         }
         if (hh == 1 && hand) {
@@ -3515,12 +3490,8 @@ __device__ __forceinline__ void lds_replay_loader(const Params& p, State s, int 
             for (int h = 0; h < H; ++h) {
                 const int sl = sl0 + h;
                 if (sl < len) {
-#if !(defined(HE_REPLAY_DIAG) && HE_REPLAY_DIAG == 1)
                     // table_greeks_kernel's record, here from the row itself
                     B[h] = p.record_metrics ? replay_greeks(p, A[h].x, A[h].y) : make_float4(0.f, 0.f, 0.f, 0.f);
-#else
-                    B[h] = make_float4(0.5f, 0.01f, -0.5f, 0.0f);
-#endif
                     L.mk[wb][sl][le] = A[h];
                     L.gd[wb][sl][le] = make_float2(B[h].x, B[h].z);
                     L.gg[wb][sl][le] = B[h].y;
@@ -3762,15 +3733,10 @@ __device__ __forceinline__ void lds_replay_stepper(const Params& p, State s, con
                 const double optv = ((double)cc * (double)post.C) * 100.0 + ((double)qq * (double)post.P) * 100.0;
                 so.pv = ((double)(c_shares_f * post.S) + optv) + e.cash;
                 so.pnl = so.pv - pv_prev;
-#if defined(HE_REPLAY_DIAG) && HE_REPLAY_DIAG == 4  // diagnostic build: reciprocal multiplies, not divisions
-                const double ps = so.pnl * c_inv_252;
-                const double rpc = (-c_w) * (fabs(ps) * c_inv_252);
-#else
                 // the division core (div_f64_core): finite P&L on an ordinary table, shares_to_hedge
                 // and the denominator normal (fast_replay_config); -0.2 %, r05s26_ab_replay_div_core.txt
                 const double ps = div_f64_core(so.pnl, c_shares_d);
                 const double rpc = (-c_w) * div_f64_core(fabs(ps), e.den);
-#endif
                 const double tcp = c_lam * so.tc;
                 const double thp = c_theta * div_int_by((double)(T - (int32_t)e.t), 252.0, c_inv_252);
                 so.reward = (rpc - tcp) - thp;
@@ -3781,10 +3747,8 @@ __device__ __forceinline__ void lds_replay_stepper(const Params& p, State s, con
                 step_env<false, FAST, true>(p, e, pre, post, ak.x, ak.y, pv_last, so);
             }
             pv_last = so.pv;
-#if !(defined(HE_REPLAY_DIAG) && HE_REPLAY_DIAG == 3)  // diagnostic build: no reward / done stores
             if (!POL || grew) grew[koff + i] = (float)so.reward;
             if (!POL || gterm) gterm[koff + i] = so.term ? 1 : 0;
-#endif
             if constexpr (POL) {
                 // step_body's POL sums, in step order, and the record of a finished episode
                 acc[0] = acc[0] + so.reward;
@@ -3868,23 +3832,15 @@ __device__ __forceinline__ void lds_replay_stepper(const Params& p, State s, con
     auto run = [&](auto full) {
         LDS_BAR();  // block 0 loaded
         for (int b = 0; b < nfull; ++b) {
-#if defined(HE_REPLAY_DIAG) && HE_REPLAY_DIAG == 2
-            LDS_BAR();  // diagnostic build: the steppers only keep the barrier count
-            continue;
-#endif
             const int buf = b & 1;
 #pragma unroll
             for (int sl = 0; sl < kLdsM; ++sl) {
                 const int k = b * kLdsM + sl;
-#if defined(HE_REPLAY_DIAG) && HE_REPLAY_DIAG == 5  // diagnostic build: no action loads
-                const float2 ak = make_float2(0.3f * (float)(sl - 4), -0.2f);
-#else
                 const float2 ak = ra[sl % D];
                 if constexpr (!POL) {
                     const int kn = k + D;
                     ra[sl % D] = ld2(gact, (int64_t)(kn < k_steps ? kn : k_steps - 1) * N + i);
                 }
-#endif
                 step(buf, sl, k, ak, full);
             }
             LDS_BAR();  // buffer b & 1 handed back, block b + 1 loaded
@@ -4208,11 +4164,10 @@ struct he_env {
     bool fuse_market = true;  // rollouts: next block's market in the step grid (HE_FUSED_MARKET=0: side stream)
     bool lds_rollout = true;  // he_rollout (GBM, no book): lds_rollout_kernel (HE_LDS_ROLLOUT=0: tile kernels)
     // lds_rollout_kernel's grid: at most this many workgroups, each looping over 64-env tiles
-    // (0: one workgroup per tile).  The device's resident count (CUs x workgroups per CU) unless
-    // HE_LDS_PERSIST=0; HE_LDS_MAX_GRID=<n> caps it (tests: many tiles per workgroup).
+    // (0: one workgroup per tile).  The device's resident count (CUs x workgroups per CU);
+    // HE_LDS_MAX_GRID=<n> caps it (tests: many tiles per workgroup).
     int64_t lds_grid = -1;    // -1: not computed yet
     int64_t lds_grid_cap = 0; // HE_LDS_MAX_GRID
-    bool lds_persist = true;
     bool lds_policy = true;   // he_rollout_policy on lds_rollout_kernel<..., POL> (HE_LDS_POLICY=0: the tile kernels)
     int32_t prefetch_mode = 0; // 0 auto, 1 never, 2 always: market_kernel(b+1) on `xs` during block b
     hipStream_t xs = nullptr; // library side stream for market prefetch
@@ -4510,114 +4465,80 @@ static void launch_reset(he_env* env, const int64_t* ids, int64_t count, float* 
                        env->cur, ids, count, obs, inf, eps);
 }
 
+// Every timed route launches through here.  he_time_next_step's events are consumed (one-shot)
+// and bracket exactly this dispatch (hipExtLaunchKernelGGL); without them, a plain launch.
+// The arguments are converted to the kernel's parameter types first: hipExtLaunchKernelGGL
+// packs what it is given.
+template <class... P, class... A>
+static void launch_timed(he_env* env, void (*kern)(P...), dim3 grid, dim3 block, hipStream_t st, const A&... args) {
+    hipEvent_t a = (hipEvent_t)env->ev_start, b = (hipEvent_t)env->ev_stop;
+    env->ev_start = env->ev_stop = nullptr;
+    if (a) hipExtLaunchKernelGGL(kern, grid, block, 0, st, a, b, 0, static_cast<P>(args)...);
+    else hipLaunchKernelGGL(kern, grid, block, 0, st, static_cast<P>(args)...);
+}
+
+// Runtime flags to template arguments: pick(f, b0, b1, ...) calls f(std::bool_constant<b0>{},
+// std::bool_constant<b1>{}, ...).  f prunes the combinations that have no kernel with
+// `if constexpr`, so the code object holds the instances that are launched and no others.
+template <class F>
+static void pick(F&& f) {
+    f();
+}
+template <class F, class... B>
+static void pick(F&& f, bool b, B... rest) {
+    if (b) pick([&](auto... t) { f(std::true_type{}, t...); }, rest...);
+    else pick([&](auto... t) { f(std::false_type{}, t...); }, rest...);
+}
+
+// k steps of the current block from slot0 (the market-tile kernels)
 template <int MODE, bool BOOK, bool FAST, bool GS>
-static void launch_step_gs(he_env* env, const Params& p, const Io& io, bool info, int k, int slot0,
-                           hipStream_t st) {
-    int64_t blocks = (env->cfg.n_envs + kEpb - 1) / kEpb;
-    if (io.pol_on) {  // policy rollouts (any k)
+static void launch_step(he_env* env, const Params& p, const Io& io, bool info, int k, int slot0, hipStream_t st) {
+    const dim3 grid((unsigned)((env->cfg.n_envs + kEpb - 1) / kEpb)), block(kBlock);
+    if (io.pol_on) {  // policy rollouts (any k): a plain launch, he_time_next_step's events stay armed
         void (*pk)(Params, State, Io, int, int) = step_kernel<MODE, false, false, BOOK, FAST, true, GS>;
-        hipLaunchKernelGGL(pk, dim3((unsigned)blocks), dim3(kBlock), 0, st, p, env->s, io, k, slot0);
+        hipLaunchKernelGGL(pk, grid, block, 0, st, p, env->s, io, k, slot0);
         return;
     }
-    if (k == 1 && !info && !io.sums) {  // he_step (rollouts keep the episode summaries)
+    const bool single = k == 1 && !io.sums;  // he_step (rollouts keep the episode summaries)
+    if (single && !info) {
         constexpr bool REPLAY = (MODE == HE_MODE_REPLAY);
         const Params* pc = env->dparams + (REPLAY ? 0 : env->cur_buf);
         const float4* tA = REPLAY ? p.rec : p.tileA;
         const float4* tB = REPLAY ? p.recg : p.tileB;
         StepIo sio{io.act, io.obs, io.rew, io.term, io.trunc, io.tobs, io.sig, io.sig_cnt, io.sig_seq};
         if (env->vne_on && io.obs && io.rew && io.term && io.tobs) {  // + the eval VecNormalize step
-            hipEvent_t a = (hipEvent_t)env->ev_start, b = (hipEvent_t)env->ev_stop;
-            env->ev_start = env->ev_stop = nullptr;
-            hipExtLaunchKernelGGL((step1_vne_kernel<MODE, BOOK, FAST, GS>), dim3((unsigned)blocks), dim3(kBlock), 0, st,
-                                  a, b, 0, pc, p.n, tA, tB, (const double*)p.tileC, env->s, sio, slot0, env->vne);
+            launch_timed(env, step1_vne_kernel<MODE, BOOK, FAST, GS>, grid, block, st, pc, p.n, tA, tB, p.tileC, env->s,
+                         sio, slot0, env->vne);
             env->vn_fused = true;
-            return;
-        }
-        if (env->vn_on) {  // + the VecNormalize moments in the same launch
+        } else if (env->vn_on) {  // + the VecNormalize moments in the same launch
             vn::MomentsArgs vm = env->vn;
             vm.obs = io.obs;
             vm.reward = io.rew;
-            hipEvent_t a = (hipEvent_t)env->ev_start, b = (hipEvent_t)env->ev_stop;
-            env->ev_start = env->ev_stop = nullptr;
-            hipExtLaunchKernelGGL((step1_vn_kernel<MODE, BOOK, FAST, GS>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a,
-                                  b, 0, pc, p.n, tA, tB, (const double*)p.tileC, env->s, sio, slot0, vm);
+            launch_timed(env, step1_vn_kernel<MODE, BOOK, FAST, GS>, grid, block, st, pc, p.n, tA, tB, p.tileC, env->s,
+                         sio, slot0, vm);
             env->vn_fused = true;
-            return;
+        } else {
+            launch_timed(env, step1_kernel<MODE, BOOK, FAST, GS>, grid, block, st, pc, p.n, tA, tB, p.tileC, env->s, sio,
+                         slot0);
         }
-        if (env->ev_start) {
-            hipEvent_t a = (hipEvent_t)env->ev_start, b = (hipEvent_t)env->ev_stop;
-            env->ev_start = env->ev_stop = nullptr;
-            hipExtLaunchKernelGGL((step1_kernel<MODE, BOOK, FAST, GS>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a, b, 0,
-                                  pc, p.n, tA, tB, (const double*)p.tileC, env->s, sio, slot0);
-            return;
-        }
-        hipLaunchKernelGGL((step1_kernel<MODE, BOOK, FAST, GS>), dim3((unsigned)blocks), dim3(kBlock), 0, st, pc, p.n, tA, tB,
-                           (const double*)p.tileC, env->s, sio, slot0);
         return;
     }
-    void (*kern)(Params, State, Io, int, int);
-    if (k == 1 && !io.sums)
-        kern = info ? step_kernel<MODE, true, true, BOOK, false, false, GS>
-                    : step_kernel<MODE, false, true, BOOK, FAST, false, GS>;
-    else
-        kern = info ? step_kernel<MODE, true, false, BOOK, false, false, GS>
-                    : step_kernel<MODE, false, false, BOOK, FAST, false, GS>;
-    if (env->ev_start) {  // one-shot: bracket exactly this dispatch (hipExtLaunchKernelGGL)
-        hipEvent_t a = (hipEvent_t)env->ev_start, b = (hipEvent_t)env->ev_stop;
-        env->ev_start = env->ev_stop = nullptr;
-        hipExtLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), 0, st, a, b, 0, p, env->s, io, k, slot0);
-        return;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), 0, st, p, env->s, io, k, slot0);
-}
-
-template <int MODE, bool BOOK, bool FAST>
-static void launch_step(he_env* env, const Params& p, const Io& io, bool info, int k, int slot0,
-                        hipStream_t st) {
-    if constexpr (MODE == HE_MODE_GBM) {
-        if (!p.tile_greeks) {
-            launch_step_gs<MODE, BOOK, FAST, true>(env, p, io, info, k, slot0, st);
-            return;
-        }
-    }
-    launch_step_gs<MODE, BOOK, FAST, false>(env, p, io, info, k, slot0, st);
-}
-
-template <int MODE, bool BOOK, bool FAST, bool GS>
-static void launch_fused_gs(he_env* env, const Params& p, const Io& io, int k, int slot0, hipStream_t st) {
-    const int64_t sblocks = (env->cfg.n_envs + kEpb - 1) / kEpb;
-    const int64_t mblocks = (env->cfg.n_envs + kMktEnvs - 1) / kMktEnvs;
-    const int nb = env->cur_buf ^ 1;
-    const dim3 grid((unsigned)(sblocks + mblocks));
-    size_t pad = 0;
-    hipEvent_t a = nullptr, b = nullptr;
-    if (env->ev_start) {  // one-shot: bracket exactly this dispatch (hipExtLaunchKernelGGL)
-        a = (hipEvent_t)env->ev_start;
-        b = (hipEvent_t)env->ev_stop;
-        env->ev_start = env->ev_stop = nullptr;
-    }
-    (void)p;
-    const Params* pc = env->dparams;
-    const int32_t buf = env->cur_buf;
-    if (a)
-        hipExtLaunchKernelGGL((step_market_kernel<MODE, BOOK, FAST, GS>), grid, dim3(kBlock), pad, st, a, b, 0, pc, buf,
-                              env->s, io, k, slot0, env->cur, env->bak[nb], (int32_t)sblocks);
-    else
-        hipLaunchKernelGGL((step_market_kernel<MODE, BOOK, FAST, GS>), grid, dim3(kBlock), pad, st, pc, buf, env->s, io,
-                           k, slot0, env->cur, env->bak[nb], (int32_t)sblocks);
+    pick([&](auto single_c, auto info_c) {  // the info kernels are never FAST
+        constexpr bool SINGLE = decltype(single_c)::value, INFO = decltype(info_c)::value;
+        launch_timed(env, step_kernel<MODE, INFO, SINGLE, BOOK, FAST && !INFO, false, GS>, grid, block, st, p, env->s, io,
+                     k, slot0);
+    }, single, info);
 }
 
 // step the current block (k steps from slot0) and generate the next block into the
-// other tile buffer, one dispatch (step_market_kernel)
-template <int MODE, bool BOOK, bool FAST>
-static void launch_fused(he_env* env, const Params& p, const Io& io, int k, int slot0, hipStream_t st) {
-    if constexpr (MODE == HE_MODE_GBM) {
-        if (!p.tile_greeks) {
-            launch_fused_gs<MODE, BOOK, FAST, true>(env, p, io, k, slot0, st);
-            return;
-        }
-    }
-    launch_fused_gs<MODE, BOOK, FAST, false>(env, p, io, k, slot0, st);
+// other tile buffer, one dispatch (step_market_kernel); never with a book
+template <int MODE, bool FAST, bool GS>
+static void launch_fused(he_env* env, const Io& io, int k, int slot0, hipStream_t st) {
+    const int64_t sblocks = (env->cfg.n_envs + kEpb - 1) / kEpb;
+    const int64_t mblocks = (env->cfg.n_envs + kMktEnvs - 1) / kMktEnvs;
+    launch_timed(env, step_market_kernel<MODE, false, FAST, GS>, dim3((unsigned)(sblocks + mblocks)), dim3(kBlock), st,
+                 env->dparams, env->cur_buf, env->s, io, k, slot0, env->cur, env->bak[env->cur_buf ^ 1],
+                 (int32_t)sblocks);
 }
 
 // Start the next block: make its market tile current (generated ahead on the side
@@ -4659,7 +4580,8 @@ static bool fast_config(const he_env* env) {
 // FAST configuration with every output buffer given, and prices and cash where every
 // P&L is 0 or a normal number far from the f64 range ends (S0 and initial cash in
 // [1e-30, 1e30]: a P&L is a difference of portfolio values, a multiple of their ulp).
-static bool lds_lean_config(const he_env* env, const Io& io) {
+// outputs: the obs, reward and terminated buffers are all present.
+static bool lds_lean_config(const he_env* env, bool outputs) {
     const he_config& c = env->cfg;
     const double s0 = c.s0, ic = fabs(c.initial_cash);
     const Params& p = env->p;
@@ -4667,7 +4589,7 @@ static bool lds_lean_config(const he_env* env, const Io& io) {
     const bool normal_greeks = c.mode == HE_MODE_HESTON || (!p.tenor_small && p.g_sigma > 1e-6f && p.g_sst >= 1e-9);
     // the lean kernels' producers make rolling-ATM marks only (marks<MODE, false>)
     // (S0 <= 1e20: S / max(S0, 25) >= 1e-8 / 1e20 stays a normal f32 for the f32 obs quotient)
-    return fast_config(env) && io.obs && io.rew && io.term && s0 >= 1e-30 && s0 <= 1e20 && ic <= 1e30 &&
+    return fast_config(env) && outputs && s0 >= 1e-30 && s0 <= 1e20 && ic <= 1e30 &&
            normal_greeks && c.mark == HE_MARK_ROLLING_ATM && (c.book_size > 0 || p.T < lds_thp_rows());
 }
 
@@ -4694,70 +4616,35 @@ static he_status launch_lds_rollout(he_env* env, const Io& io, int k_total, hipS
     const int64_t blocks = (env->cfg.n_envs + kLdsEnvs - 1) / kLdsEnvs;
     const Params* pc = env->dparams;  // buffer 0's copy: the tile pointers are not used
     const bool book = env->cfg.book_size > 0, pol = io.pol_on;
-    bool lean = lds_lean_config(env, io);
-    if (pol) {   // policy rollouts may return no obs / reward / done: the lean test on the rest
-        Io o = io;
-        o.obs = o.obs ? o.obs : reinterpret_cast<float*>(16);
-        o.rew = o.rew ? o.rew : reinterpret_cast<float*>(16);
-        o.term = o.term ? o.term : reinterpret_cast<uint8_t*>(16);
-        lean = lds_lean_config(env, o);
-    }
-    void (*kern)(const Params*, State, Io, int, Market);
-    void (*kern_p)(const Params*, State, Io, int, Market);   // the persistent-grid instance
-    int threads;
-#define HE_LDS_PICK(M, B, L)                                                  \
-    do {                                                                      \
-        if (pol) {                                                            \
-            kern = lds_rollout_kernel<M, B, L, false, true>;                  \
-            kern_p = lds_rollout_kernel<M, B, L, !(B), true>;                 \
-        } else {                                                              \
-            kern = lds_rollout_kernel<M, B, L, false>;                        \
-            kern_p = lds_rollout_kernel<M, B, L, !(B)>;                       \
-        }                                                                     \
-        threads = LdsGeom<M, B>::threads;                                     \
-    } while (0)
-    if (env->cfg.mode == HE_MODE_HESTON) {
-        if (lean) {
-            if (book) HE_LDS_PICK(HE_MODE_HESTON, true, true);
-            else HE_LDS_PICK(HE_MODE_HESTON, false, true);
-        } else {
-            if (book) HE_LDS_PICK(HE_MODE_HESTON, true, false);
-            else HE_LDS_PICK(HE_MODE_HESTON, false, false);
-        }
-    } else if (book) {
-        if (lean) HE_LDS_PICK(HE_MODE_GBM, true, true);
-        else HE_LDS_PICK(HE_MODE_GBM, true, false);
-    } else {
-        if (lean) HE_LDS_PICK(HE_MODE_GBM, false, true);
-        else HE_LDS_PICK(HE_MODE_GBM, false, false);
-    }
-#undef HE_LDS_PICK
+    // policy rollouts may return no obs / reward / done: the lean test without its output condition
+    const bool lean = lds_lean_config(env, pol || (io.obs && io.rew && io.term));
+    void (*kern)(const Params*, State, Io, int, Market) = nullptr;
+    void (*kern_p)(const Params*, State, Io, int, Market) = nullptr;   // the persistent-grid instance
+    int threads = 0;
+    pick([&](auto heston_c, auto book_c, auto lean_c, auto pol_c) {
+        constexpr int MODE = decltype(heston_c)::value ? HE_MODE_HESTON : HE_MODE_GBM;
+        constexpr bool BOOK = decltype(book_c)::value, LEAN = decltype(lean_c)::value, POL = decltype(pol_c)::value;
+        kern = lds_rollout_kernel<MODE, BOOK, LEAN, false, POL>;
+        kern_p = lds_rollout_kernel<MODE, BOOK, LEAN, !BOOK, POL>;
+        threads = LdsGeom<MODE, BOOK>::threads;
+    }, env->cfg.mode == HE_MODE_HESTON, book, lean, pol);
     // the persistent grid: as many workgroups as the device holds at once (one round), each
     // looping over tiles -- past one round, workgroups that start as others finish take their
     // roles from a ticket that no longer lines up with the SIMDs they land on
     int64_t grid = blocks;
-    if (env->lds_persist) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern_p, threads, 0) == hipSuccess &&
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, env->cfg.device) == hipSuccess &&
-            per_cu > 0 && cus > 0 && grid > (int64_t)per_cu * cus)
-            grid = (int64_t)per_cu * cus;
-        (void)hipGetLastError();
-    }
+    int per_cu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern_p, threads, 0) == hipSuccess &&
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, env->cfg.device) == hipSuccess &&
+        per_cu > 0 && cus > 0 && grid > (int64_t)per_cu * cus)
+        grid = (int64_t)per_cu * cus;
+    (void)hipGetLastError();
     if (env->lds_grid_cap > 0 && grid > env->lds_grid_cap) grid = env->lds_grid_cap;
     env->lds_grid = grid;
     // with a book the persistent instance spills (13 VGPRs) and measured slower (config 4
     // 5.64 vs 5.48 ms, config 5 1.49 vs 1.46 ms, profiles/r06bal_*): one workgroup per tile there
     if (grid < blocks && !book) kern = kern_p;
     else grid = blocks;
-    if (env->ev_start) {  // one-shot: bracket exactly this dispatch
-        hipEvent_t a = (hipEvent_t)env->ev_start, b = (hipEvent_t)env->ev_stop;
-        env->ev_start = env->ev_stop = nullptr;
-        hipExtLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), 0, st, a, b, 0, pc, env->s, io, k_total,
-                              env->cur);
-    } else {
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), 0, st, pc, env->s, io, k_total, env->cur);
-    }
+    launch_timed(env, kern, dim3((unsigned)grid), dim3(threads), st, pc, env->s, io, k_total, env->cur);
     HE_HIP(env, hipGetLastError());
     env->block_pos = env->cfg.market_block;
     env->next_state = 0;
@@ -4766,10 +4653,10 @@ static he_status launch_lds_rollout(he_env* env, const Io& io, int k_total, hipS
 
 // he_rollout in replay mode through lds_replay_kernel (HE_LDS_ROLLOUT=0: step_kernel): every
 // output buffer given, episodes of at least one LDS block (at most one episode end per env
-// and block), autoreset (he_rollout's precondition).
-static bool lds_replay_eligible(const he_env* env, const Io& io) {
-    return env->lds_rollout && env->cfg.autoreset && env->p.T >= kLdsM && env->n_paths > 0 && io.obs && io.rew &&
-           io.term;
+// and block), autoreset (he_rollout's precondition).  outputs: the obs, reward and terminated
+// buffers are all present.
+static bool lds_replay_eligible(const he_env* env, bool outputs) {
+    return env->lds_rollout && env->cfg.autoreset && env->p.T >= kLdsM && env->n_paths > 0 && outputs;
 }
 
 // The configuration the FAST replay steppers are specialised for (step_env / make_obs with
@@ -4783,29 +4670,18 @@ static bool fast_replay_config(const he_env* env) {
 
 // he_rollout_policy in replay mode through lds_replay_kernel<..., POL> (the obs / reward /
 // terminated buffers may be absent)
-static bool lds_replay_policy_eligible(const he_env* env, const Io& io) {
-    Io o = io;
-    o.obs = o.obs ? o.obs : reinterpret_cast<float*>(16);   // (lds_replay_eligible's output test only)
-    o.rew = o.rew ? o.rew : reinterpret_cast<float*>(16);
-    o.term = o.term ? o.term : reinterpret_cast<uint8_t*>(16);
-    return env->lds_policy && lds_replay_eligible(env, o);
+static bool lds_replay_policy_eligible(const he_env* env) {
+    return env->lds_policy && lds_replay_eligible(env, true);
 }
 
 static he_status launch_lds_replay(he_env* env, const Io& io, int k_total, hipStream_t st) {
     const int64_t blocks = (env->cfg.n_envs + kLdsEnvs - 1) / kLdsEnvs;
-    const Params* pc = env->dparams;
     // policy rollouts on the generic steppers in every configuration (the FAST instance with the
     // policy's sums spilled 25 VGPRs)
     const bool fast = fast_replay_config(env);
     void (*kern)(const Params*, State, Io, int) =
         io.pol_on ? lds_replay_kernel<false, true> : (fast ? lds_replay_kernel<true> : lds_replay_kernel<false>);
-    if (env->ev_start) {  // one-shot: bracket exactly this dispatch
-        hipEvent_t a = (hipEvent_t)env->ev_start, b = (hipEvent_t)env->ev_stop;
-        env->ev_start = env->ev_stop = nullptr;
-        hipExtLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, st, a, b, 0, pc, env->s, io, k_total);
-    } else {
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, st, pc, env->s, io, k_total);
-    }
+    launch_timed(env, kern, dim3((unsigned)blocks), dim3(256), st, env->dparams, env->s, io, k_total);
     HE_HIP(env, hipGetLastError());
     return HE_OK;
 }
@@ -4818,9 +4694,10 @@ static he_status launch_steps(he_env* env, Io io, bool info, int k_total, void* 
     hipStream_t st = (hipStream_t)stream;
     io.sums = rollout && !io.pol_on;
     if (c.mode == HE_MODE_REPLAY) {
-        if (rollout && !info && !io.pol_on && lds_replay_eligible(env, io)) return launch_lds_replay(env, io, k_total, st);
-        if (io.pol_on && lds_replay_policy_eligible(env, io)) return launch_lds_replay(env, io, k_total, st);
-        launch_step<HE_MODE_REPLAY, false, false>(env, env->p, io, info, k_total, 0, st);
+        if (rollout && !info && !io.pol_on && lds_replay_eligible(env, io.obs && io.rew && io.term))
+            return launch_lds_replay(env, io, k_total, st);
+        if (io.pol_on && lds_replay_policy_eligible(env)) return launch_lds_replay(env, io, k_total, st);
+        launch_step<HE_MODE_REPLAY, false, false, false>(env, env->p, io, info, k_total, 0, st);
         HE_HIP(env, hipGetLastError());
         return HE_OK;
     }
@@ -4855,34 +4732,16 @@ static he_status launch_steps(he_env* env, Io io, bool info, int k_total, void* 
         if (io.rew) sub.rew = io.rew + (int64_t)done * N;
         if (io.term) sub.term = io.term + (int64_t)done * N;
         Params p = tile_params(env, env->cur_buf);
-        const bool book = c.book_size > 0;
-        const bool fast = fast_config(env);
-        if (fuse) {  // never with a book (see above)
-            if (c.mode == HE_MODE_GBM) {
-                if (fast) launch_fused<HE_MODE_GBM, false, true>(env, p, sub, k, env->block_pos, st);
-                else launch_fused<HE_MODE_GBM, false, false>(env, p, sub, k, env->block_pos, st);
-            } else {
-                if (fast) launch_fused<HE_MODE_HESTON, false, true>(env, p, sub, k, env->block_pos, st);
-                else launch_fused<HE_MODE_HESTON, false, false>(env, p, sub, k, env->block_pos, st);
+        const bool heston = c.mode == HE_MODE_HESTON;
+        pick([&](auto heston_c, auto book_c, auto fast_c, auto gs_c) {
+            constexpr int MODE = decltype(heston_c)::value ? HE_MODE_HESTON : HE_MODE_GBM;
+            constexpr bool BOOK = decltype(book_c)::value, FAST = decltype(fast_c)::value, GS = decltype(gs_c)::value;
+            if constexpr (MODE == HE_MODE_GBM || !GS) {   // GS (the obs greeks made in the step kernel): GBM only
+                if (!fuse) launch_step<MODE, BOOK, FAST, GS>(env, p, sub, info, k, env->block_pos, st);
+                else if constexpr (!BOOK) launch_fused<MODE, FAST, GS>(env, sub, k, env->block_pos, st);  // (see above)
             }
-            env->next_state = 2;  // ordered on st before the next block's steps
-        } else if (c.mode == HE_MODE_GBM) {
-            if (book) {
-                if (fast) launch_step<HE_MODE_GBM, true, true>(env, p, sub, info, k, env->block_pos, st);
-                else launch_step<HE_MODE_GBM, true, false>(env, p, sub, info, k, env->block_pos, st);
-            } else {
-                if (fast) launch_step<HE_MODE_GBM, false, true>(env, p, sub, info, k, env->block_pos, st);
-                else launch_step<HE_MODE_GBM, false, false>(env, p, sub, info, k, env->block_pos, st);
-            }
-        } else {
-            if (book) {
-                if (fast) launch_step<HE_MODE_HESTON, true, true>(env, p, sub, info, k, env->block_pos, st);
-                else launch_step<HE_MODE_HESTON, true, false>(env, p, sub, info, k, env->block_pos, st);
-            } else {
-                if (fast) launch_step<HE_MODE_HESTON, false, true>(env, p, sub, info, k, env->block_pos, st);
-                else launch_step<HE_MODE_HESTON, false, false>(env, p, sub, info, k, env->block_pos, st);
-            }
-        }
+        }, heston, c.book_size > 0, fast_config(env), !heston && !p.tile_greeks);
+        if (fuse) env->next_state = 2;  // ordered on st before the next block's steps
         HE_HIP(env, hipGetLastError());
         env->block_pos += k;
         done += k;
@@ -5040,8 +4899,6 @@ he_status he_create(const he_config* cfg, he_env** out) {
         {
             const char* ev = getenv("HE_FUSED_MARKET");
             env->fuse_market = !(ev && ev[0] == '0');
-            const char* ep = getenv("HE_LDS_PERSIST");
-            env->lds_persist = !(ep && ep[0] == '0');
             const char* eg = getenv("HE_LDS_MAX_GRID");
             env->lds_grid_cap = eg ? atoll(eg) : 0;
         }

@@ -11,7 +11,6 @@ env_method, env_is_wrapped) with SB3's auto-reset semantics
 Every env's state lives on the device; one `he_step` launch advances all of
 them.  `step_tensors` is the zero-copy path for GPU-resident learners.
 """
-import os
 import time
 import weakref
 
@@ -172,8 +171,6 @@ class HedgingVecEnv:
                 cfg.book[k].strike = float(o["strike"])
                 cfg.book[k].barrier = float(o.get("barrier", 0.0))
                 cfg.book[k].quantity = float(o["quantity"])
-        if os.environ.get("CANTORRL_NO_PREFETCH"):
-            market_prefetch = False
         # 0 auto (rollouts, or single steps from 131,072 envs), 1 never, 2 always
         cfg.market_prefetch = 0 if market_prefetch == "auto" else (2 if market_prefetch else 1)
         base_seed = int(seed if seed is not None else gen.get("seed", 42))
