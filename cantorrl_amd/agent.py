@@ -70,7 +70,8 @@ HA_POLICY_ABI_VERSION = 1
 EXPORTS = ["ha_version", "ha_last_error", "ha_create", "ha_destroy", "ha_step", "ha_accumulate", "ha_host_step",
            "ha_policy_last_error", "ha_policy_create", "ha_policy_destroy", "ha_policy_update", "ha_policy_step",
            "ha_gae", "ha_host_policy_step", "ha_host_gae", "ha_lstm_seq_workspace_bytes", "ha_lstm_seq_forward",
-           "ha_lstm_seq_backward", "ha_host_lstm_seq_forward", "ha_host_lstm_seq_backward"]
+           "ha_lstm_seq_backward", "ha_host_lstm_seq_forward", "ha_host_lstm_seq_backward",
+           "ha_lstm_seq_weight_grads_workspace_bytes", "ha_lstm_seq_weight_grads", "ha_host_lstm_seq_weight_grads"]
 
 _F = ctypes.POINTER(ctypes.c_float)
 _D = ctypes.POINTER(ctypes.c_double)
@@ -130,6 +131,9 @@ def load(path=LIB_PATH):
         "ha_lstm_seq_backward": (i32, [i64, i64, i64] + [vp] * 4),
         "ha_host_lstm_seq_forward": (i32, [i64, i64, i64] + [vp] * 3),
         "ha_host_lstm_seq_backward": (i32, [i64, i64, i64] + [vp] * 2),
+        "ha_lstm_seq_weight_grads_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64]),
+        "ha_lstm_seq_weight_grads": (i32, [i64, i64, i64] + [vp] * 5),
+        "ha_host_lstm_seq_weight_grads": (i32, [i64, i64, i64] + [vp] * 3),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

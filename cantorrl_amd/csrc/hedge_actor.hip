@@ -25,7 +25,8 @@
 // log-probability, blockIdx.y = 1 runs the critic's on h_vf / c_vf and ends in the value.  Both
 // stage the same obs; registers and LDS stay at actor_kernel's figures.  gae_kernel (ha_gae) is
 // one thread per env over [K][n] arrays.  lstm_seq_fwd_kernel / lstm_seq_bwd_kernel (the PPO update's
-// LSTM over a stored sequence, forward and backward) are described where they stand.
+// LSTM over a stored sequence, forward and backward) and lstm_wgrad_kernel / lstm_wgrad_reduce_kernel
+// (its weight gradients) are described where they stand.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -837,6 +838,277 @@ ha_status check_seq_bwd(int64_t n_nets, const void* starts, const ha_lstm_seq_bw
     return HE_OK;
 }
 
+// ---------------------------------------------------------------- the LSTM's weight gradients
+// lstm_wgrad_kernel / lstm_wgrad_reduce_kernel (ha_lstm_seq_weight_grads, contract W1-W4).
+//   lstm_wgrad_kernel   grid (chunks, 4 groups of 128 gate rows, n_nets), 4 waves.  Wave w owns gate
+//             rows u0 = 128 group + 32 w .. u0 + 31 against all of z, padded to five 32-column tiles:
+//             five f32 accumulators D[u][column], independent, so the instruction's 64-cycle
+//             dependent latency is covered.  The MFMA's k is the ROW index: lane l feeds
+//             A = dg[r + (l >> 5)][u0 + (l & 31)] straight from global (a coalesced pair of 128-byte
+//             lines per k-step, shared by the five tiles) and B = z[r + (l >> 5)][32 n + (l & 31)]
+//             from LDS, so a block's 64 k-steps are W1's chain over its 128 rows.  z is built per
+//             workgroup in LDS in sub-blocks of 32 rows, double-buffered, in the column order
+//             [h_prev 128 | x 13 | 1 | 0 x 18] (16-byte stores of h; the chain runs over rows, so the
+//             column order is free): the next sub-block's x, h (row r - B, or h0), start flags and A
+//             operands are loaded before the current one's 80 MFMAs and stored after them, one
+//             barrier per sub-block.  Rows past R load from row R - 1 and are replaced by +0: the
+//             padding terms of W1.  After each block the accumulators are added into 80 f64
+//             registers a lane (W2; v_add_f64 is IEEE) and zeroed; the chunk's p_c goes to the
+//             workspace as [512][142] f64.
+//   lstm_wgrad_reduce_kernel   one thread per output adds its p_c over the chunks in order and
+//             rounds once (W3, W4).
+constexpr int kWgSub = 32;                  // rows of a staged sub-block: 16 k-steps
+constexpr int kWgSteps = kWgSub / 2;
+constexpr int kWgTiles = 5;                 // 32-column tiles of z
+constexpr int kWgCols = 32 * kWgTiles;      // 160
+constexpr int kWgXcol = kHid;               // z's LDS columns: h_prev at 0, x at 128, the ones column at 141
+constexpr int64_t kWgChunkRows = (int64_t)HA_WGRAD_BLOCK * HA_WGRAD_CHUNK;
+constexpr size_t kWgPartial = (size_t)kGates * kKp;   // f64 of one chunk's p_c
+static_assert(HA_WGRAD_BLOCK % kWgSub == 0 && HA_WGRAD_BLOCK >= kWgSub && HA_WGRAD_CHUNK >= 1, "whole sub-blocks");
+static_assert(kKp <= kWgCols && kWgSub * kHid == 4 * 4 * kThreads && kWgSub * kObs <= 2 * kThreads, "staging passes");
+
+struct WgradParams {
+    int64_t R, B, n_chunks;
+    const float* x;
+    const uint8_t* start;
+    ha_lstm_seq_wgrad net[2];
+    double* ws;
+};
+
+struct WgradTile {
+    float z[2][kWgSub][kWgCols];   // 40,960 B
+};
+
+// one sub-block's loads, held in registers across the MFMAs of the sub-block before it: raw values from
+// clamped addresses (rows past R read row R - 1); wgrad_store / wgrad_operands replace them by +0.
+// Nothing here depends on a loaded value, so no load is waited for before the MFMAs.
+struct WgradStage {
+    float4 h[4];
+    float x[2];
+    float a[kWgSteps];
+    uint8_t fresh[4];
+};
+
+// the last in-range row of the sub-block at rb, relative to rb: 31 when it is whole, negative past R
+__device__ __forceinline__ int wgrad_last_row(int64_t rb, int64_t R) {
+    const int64_t lim = R - 1 - rb;
+    return (int)(lim < kWgSub - 1 ? lim : kWgSub - 1);
+}
+
+// aoff = (lane >> 5) 512 + u0 + (lane & 31): the lane's part of its A operand's address
+__device__ __forceinline__ void wgrad_load(WgradStage& st, const WgradParams& p, const ha_lstm_seq_wgrad& nt,
+                                           int64_t rb, int tid, unsigned aoff) {
+    const int64_t B = p.B;
+    const int lim = wgrad_last_row(rb, p.R);
+    if (lim == kWgSub - 1 && rb >= B) {
+        // a whole sub-block past the first step: wave-uniform bases, the lane's part a 32-bit offset
+        const float* hb = nt.h + (rb - B) * kHid;
+        const uint8_t* eb = p.start + rb;
+        const float* xb = p.x + rb * kObs;
+        const float* ab = nt.d_gates + rb * kGates;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            st.h[i] = *(const float4*)(hb + i * 4 * kThreads + 4u * (unsigned)tid);
+            st.fresh[i] = eb[i * (kThreads >> 5) + ((unsigned)tid >> 5)];
+        }
+        st.x[0] = xb[(unsigned)tid];
+        st.x[1] = xb[(unsigned)tid < kWgSub * kObs - kThreads ? kThreads + (unsigned)tid : 0u];
+#pragma unroll
+        for (int s = 0; s < kWgSteps; ++s) st.a[s] = (ab + 2 * s * kGates)[aoff];
+        return;
+    }
+    const int hi = (int)(aoff >> 9);
+    const int xlim = lim * kObs + kObs - 1;   // the last in-range element of x relative to rb's first
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int idx = tid + i * kThreads, row = idx >> 5;
+        const int64_t r = rb + (row < lim ? row : lim);
+        const float* src = r >= B ? nt.h + (r - B) * kHid : nt.h0 + r * kHid;
+        st.h[i] = *(const float4*)(src + 4 * (idx & 31));
+        st.fresh[i] = p.start[r];
+    }
+    const float* xb = p.x + rb * kObs;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int idx = tid + i * kThreads;
+        st.x[i] = xb[idx < xlim ? idx : xlim];
+    }
+    const float* ab = nt.d_gates + rb * kGates + (aoff & 511u);
+#pragma unroll
+    for (int s = 0; s < kWgSteps; ++s) {
+        const int row = 2 * s + hi;
+        st.a[s] = ab[(row < lim ? row : lim) * kGates];
+    }
+}
+
+__device__ __forceinline__ void wgrad_store(float (*z)[kWgCols], const WgradStage& st, int64_t rb, int64_t R, int tid) {
+    const int lim = wgrad_last_row(rb, R);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int idx = tid + i * kThreads, row = idx >> 5;
+        const bool keep = (row <= lim) & (st.fresh[i] == 0);
+        const float4 v = st.h[i];
+        *(float4*)&z[row][4 * (idx & 31)] = make_float4(keep ? v.x : 0.0f, keep ? v.y : 0.0f, keep ? v.z : 0.0f, keep ? v.w : 0.0f);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int idx = tid + i * kThreads;
+        if (idx < kWgSub * kObs) {
+            const int row = idx / kObs;
+            z[row][kWgXcol + (idx - row * kObs)] = row <= lim ? st.x[i] : 0.0f;
+        }
+    }
+    if (tid < kWgSub) z[tid][kWgXcol + kObs] = tid <= lim ? 1.0f : 0.0f;
+}
+
+// the A operands of the sub-block at rb
+__device__ __forceinline__ void wgrad_operands(float* ac, const WgradStage& st, int64_t rb, int64_t R, int hi) {
+    const int lim = wgrad_last_row(rb, R);
+#pragma unroll
+    for (int s = 0; s < kWgSteps; ++s) ac[s] = 2 * s + hi <= lim ? st.a[s] : 0.0f;
+}
+
+__global__ __launch_bounds__(kThreads) void lstm_wgrad_kernel(const WgradParams p) {
+    __shared__ WgradTile t;
+    const int tid = threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int col = lane & 31, hi = lane >> 5;
+    const bool second = blockIdx.z != 0;
+    const ha_lstm_seq_wgrad nt = second ? p.net[1] : p.net[0];
+    const int64_t R = p.R;
+    const int64_t r0 = (int64_t)blockIdx.x * kWgChunkRows;   // the chunk's first row (< R)
+    const int64_t rows = R - r0 < kWgChunkRows ? R - r0 : kWgChunkRows;
+    const int n_sub = (int)((rows + HA_WGRAD_BLOCK - 1) / HA_WGRAD_BLOCK) * (HA_WGRAD_BLOCK / kWgSub);
+    const int u0 = (int)blockIdx.y * kHid + wave * 32;
+    const unsigned aoff = (unsigned)(hi * kGates + u0 + col);
+
+    // the zero columns of both halves, and the first sub-block
+    for (int idx = tid; idx < 2 * kWgSub * (kWgCols - kKp); idx += kThreads) {
+        const int rw = idx / (kWgCols - kKp);
+        t.z[rw >> 5][rw & 31][kKp + (idx - rw * (kWgCols - kKp))] = 0.0f;
+    }
+    WgradStage st;
+    wgrad_load(st, p, nt, r0, tid, aoff);
+    wgrad_store(t.z[0], st, r0, R, tid);
+    float ac[kWgSteps];
+    wgrad_operands(ac, st, r0, R, hi);
+    __syncthreads();
+
+    f32x16 acc[kWgTiles];
+    double d[kWgTiles][16];
+#pragma unroll
+    for (int n = 0; n < kWgTiles; ++n)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            acc[n][r] = 0.0f;
+            d[n][r] = 0.0;
+        }
+
+    for (int sb = 0; sb < n_sub; ++sb) {
+        const bool more = sb + 1 < n_sub;
+        const int64_t rn = r0 + (int64_t)(sb + 1) * kWgSub;
+        if (more) wgrad_load(st, p, nt, rn, tid, aoff);
+        __builtin_amdgcn_sched_barrier(0);   // the loads are issued before the MFMAs, their uses come after
+        const float* zb = &t.z[sb & 1][hi][col];
+#pragma unroll
+        for (int s = 0; s < kWgSteps; ++s) {
+#pragma unroll
+            for (int n = 0; n < kWgTiles; ++n)
+                acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[s], zb[2 * s * kWgCols + 32 * n], acc[n], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) {
+            wgrad_store(t.z[(sb + 1) & 1], st, rn, R, tid);
+            wgrad_operands(ac, st, rn, R, hi);
+        }
+        __syncthreads();
+        if ((sb & (HA_WGRAD_BLOCK / kWgSub - 1)) == HA_WGRAD_BLOCK / kWgSub - 1) {   // a block is complete: W2
+#pragma unroll
+            for (int n = 0; n < kWgTiles; ++n)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    d[n][r] += (double)acc[n][r];
+                    acc[n][r] = 0.0f;
+                }
+        }
+    }
+
+    // p_c[u][k]: tile n < 4 holds k = 13 + 32 n + col, tile 4 the x columns and the bias column
+    double* out = p.ws + ((size_t)(second ? p.n_chunks : 0) + blockIdx.x) * kWgPartial;
+#pragma unroll
+    for (int n = 0; n < kWgTiles; ++n) {
+        const int k = n < 4 ? kObs + 32 * n + col : (col < kObs ? col : (col == kObs ? kKx : -1));
+        if (k < 0) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) out[(size_t)(u0 + (r & 3) + 8 * (r >> 2) + 4 * hi) * kKp + k] = d[n][r];
+    }
+}
+
+// grid (blocks of 256 outputs, n_nets)
+__global__ __launch_bounds__(256) void lstm_wgrad_reduce_kernel(const WgradParams p) {
+    const unsigned idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= kWgPartial) return;
+    const bool second = blockIdx.y != 0;
+    const ha_lstm_seq_wgrad nt = second ? p.net[1] : p.net[0];
+    const double* __restrict__ src = p.ws + (size_t)(second ? p.n_chunks : 0) * kWgPartial + idx;
+    double total = 0.0;
+    for (int64_t c = 0; c < p.n_chunks; ++c) total += src[c * kWgPartial];
+    const float v = (float)total;
+    const int u = idx / kKp, k = idx - u * kKp;
+    if (k < kObs) nt.d_w_ih[u * kObs + k] = v;
+    else if (k < kKx) nt.d_w_hh[u * kHid + (k - kObs)] = v;
+    else nt.d_b[u] = v;
+}
+
+// one row's terms of W1 for every (u, k): s[u][k] = fmaf(dg[u], z[k], s[u][k]).  fmaf is correctly
+// rounded whether libm computes it or the CPU's FMA unit; where the CPU has one, the second copy
+// lets the k loop run on it eight wide (the same bits, an order of magnitude sooner).
+#define HA_WGRAD_ROW_BODY                                                   \
+    for (int u = 0; u < kGates; ++u) {                                      \
+        const float a = dg[u];                                              \
+        float* su = s + (size_t)u * kKp;                                    \
+        for (int k = 0; k < kKp; ++k) su[k] = __builtin_fmaf(a, z[k], su[k]); \
+    }
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+#define HA_WGRAD_FMA_COPY 1
+__attribute__((target("avx2,fma"))) void wgrad_row_fma(const float* __restrict__ dg, const float* __restrict__ z,
+                                                       float* __restrict__ s) {
+    HA_WGRAD_ROW_BODY
+}
+#endif
+void wgrad_row(const float* __restrict__ dg, const float* __restrict__ z, float* __restrict__ s) {
+#ifdef HA_WGRAD_FMA_COPY
+    static const bool fma_unit = __builtin_cpu_supports("avx2") && __builtin_cpu_supports("fma");
+    if (fma_unit) return wgrad_row_fma(dg, z, s);
+#endif
+    HA_WGRAD_ROW_BODY
+}
+#undef HA_WGRAD_ROW_BODY
+
+int64_t wgrad_chunks(int64_t L, int64_t B) { return (L * B + kWgChunkRows - 1) / kWgChunkRows; }
+
+ha_status check_wgrad(int64_t n_nets, int64_t L, int64_t B, const void* x, const void* starts,
+                      const ha_lstm_seq_wgrad* nets, uintptr_t mask) {
+    ha_status st = check_seq(n_nets, L, B);
+    if (st != HE_OK) return st;
+    if (wgrad_chunks(L, B) > 0x7fffffffll) {
+        char m[200];
+        snprintf(m, sizeof m, "L B = %lld rows: more than 2^31 - 1 chunks of %lld rows", (long long)(L * B),
+                 (long long)kWgChunkRows);
+        return fail_to(nullptr, HE_ESHAPE, m);
+    }
+    if (!nets) return fail_to(nullptr, HE_EINVAL, "nets is NULL");
+    if (!x || bad_ptr(starts, mask))
+        return fail_to(nullptr, HE_EINVAL, "x must be non-NULL, episode_starts non-NULL and 16-byte aligned");
+    for (int64_t k = 0; k < n_nets; ++k) {
+        const ha_lstm_seq_wgrad& n = nets[k];
+        if (bad_ptr(n.d_gates, mask) || bad_ptr(n.h, mask) || bad_ptr(n.h0, mask) || bad_ptr(n.d_w_ih, mask) ||
+            bad_ptr(n.d_w_hh, mask) || bad_ptr(n.d_b, mask))
+            return fail_to(nullptr, HE_EINVAL, "a tensor of ha_lstm_seq_wgrad is NULL or not 16-byte aligned");
+    }
+    return HE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1257,6 +1529,79 @@ ha_status ha_host_lstm_seq_backward(int64_t n_nets, int64_t L, int64_t B, const 
                     dhr[j] = fresh ? 0.0f : acc;
                 }
             }
+        }
+    }
+    return HE_OK;
+}
+
+size_t ha_lstm_seq_weight_grads_workspace_bytes(int64_t n_nets, int64_t L, int64_t B) {
+    if ((n_nets != 1 && n_nets != 2) || L < 1 || B < 1 || L > ((int64_t)1 << 30) || B > ((int64_t)1 << 30)) return 0;
+    const int64_t chunks = wgrad_chunks(L, B);
+    return chunks > 0x7fffffffll ? 0 : (size_t)n_nets * (size_t)chunks * kWgPartial * sizeof(double);
+}
+
+ha_status ha_lstm_seq_weight_grads(int64_t n_nets, int64_t L, int64_t B, const float* x,
+                                   const uint8_t* episode_starts, const ha_lstm_seq_wgrad* nets, void* workspace,
+                                   void* stream) {
+    ha_status st = check_wgrad(n_nets, L, B, x, episode_starts, nets, 15u);
+    if (st != HE_OK) return st;
+    if (bad_ptr(workspace, 15u)) return fail_to(nullptr, HE_EINVAL, "workspace must be non-NULL and 16-byte aligned");
+    WgradParams p;
+    memset(&p, 0, sizeof p);
+    for (int64_t k = 0; k < n_nets; ++k) p.net[k] = nets[k];
+    p.R = L * B;
+    p.B = B;
+    p.n_chunks = wgrad_chunks(L, B);
+    p.x = x;
+    p.start = episode_starts;
+    p.ws = (double*)workspace;
+    hipLaunchKernelGGL(lstm_wgrad_kernel, dim3((unsigned)p.n_chunks, kGates / kHid, (unsigned)n_nets), dim3(kThreads), 0,
+                       (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) return fail_to(nullptr, HE_EHIP, "lstm_wgrad_kernel launch failed");
+    hipLaunchKernelGGL(lstm_wgrad_reduce_kernel, dim3((unsigned)((kWgPartial + 255) / 256), (unsigned)n_nets), dim3(256),
+                       0, (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) return fail_to(nullptr, HE_EHIP, "lstm_wgrad_reduce_kernel launch failed");
+    return HE_OK;
+}
+
+ha_status ha_host_lstm_seq_weight_grads(int64_t n_nets, int64_t L, int64_t B, const float* x,
+                                        const uint8_t* episode_starts, const ha_lstm_seq_wgrad* nets) {
+    ha_status st = check_wgrad(n_nets, L, B, x, episode_starts, nets, 0u);
+    if (st != HE_OK) return st;
+    const int64_t R = L * B, chunks = wgrad_chunks(L, B);
+    std::vector<float> sv(kWgPartial);
+    std::vector<double> pv(kWgPartial), tv(kWgPartial);
+    float* s = sv.data();
+    const float zeros[kGates] = {0.0f};
+    for (int64_t k = 0; k < n_nets; ++k) {
+        const ha_lstm_seq_wgrad& n = nets[k];
+        for (size_t i = 0; i < kWgPartial; ++i) tv[i] = 0.0;
+        for (int64_t c = 0; c < chunks; ++c) {
+            for (size_t i = 0; i < kWgPartial; ++i) pv[i] = 0.0;
+            const int64_t c0 = c * kWgChunkRows, c1 = c0 + kWgChunkRows < R ? c0 + kWgChunkRows : R;
+            for (int64_t b0 = c0; b0 < c1; b0 += HA_WGRAD_BLOCK) {
+                for (size_t i = 0; i < kWgPartial; ++i) s[i] = 0.0f;
+                for (int64_t r = b0; r < b0 + HA_WGRAD_BLOCK; ++r) {   // W1, the padding terms included
+                    float z[kKp];
+                    if (r < R) {
+                        const bool fresh = episode_starts[r] != 0;
+                        const float* hp = r >= B ? n.h + (r - B) * kHid : n.h0 + r * kHid;
+                        for (int i = 0; i < kObs; ++i) z[i] = x[r * kObs + i];
+                        for (int u = 0; u < kHid; ++u) z[kObs + u] = fresh ? 0.0f : hp[u];
+                        z[kKx] = 1.0f;
+                    } else {
+                        for (int i = 0; i < kKp; ++i) z[i] = 0.0f;
+                    }
+                    wgrad_row(r < R ? n.d_gates + r * kGates : zeros, z, s);
+                }
+                for (size_t i = 0; i < kWgPartial; ++i) pv[i] += (double)s[i];   // W2
+            }
+            for (size_t i = 0; i < kWgPartial; ++i) tv[i] += pv[i];   // W3
+        }
+        for (int u = 0; u < kGates; ++u) {   // W4
+            for (int i = 0; i < kObs; ++i) n.d_w_ih[u * kObs + i] = (float)tv[(size_t)u * kKp + i];
+            for (int j = 0; j < kHid; ++j) n.d_w_hh[u * kHid + j] = (float)tv[(size_t)u * kKp + kObs + j];
+            n.d_b[u] = (float)tv[(size_t)u * kKp + kKx];
         }
     }
     return HE_OK;

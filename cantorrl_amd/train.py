@@ -16,7 +16,9 @@ Only the LSTM is a kernel: nn.LSTM has no per-step reset, so sb3_contrib's _proc
 LSTM call per time step, forward and again in autograd's backward.  Here a workgroup walks all L
 steps of its 32 envs inside one launch, actor and critic side by side.  The MLPs, the heads, the
 Gaussian log-probability, the loss and the optimizer are batched over L B rows and stay with torch.
-There is no torch fallback for the LSTM: a missing library is an error.
+There is no torch fallback for the LSTM: a missing library is an error.  The LSTM's weight gradients are
+sums of d_gates over the L B rows: blocked torch GEMMs by default (weight_grads), or with
+weight_grads="kernel" libhedgeactor's lstm_wgrad_kernel (lstm_seq_weight_grads, contract W1-W4).
 """
 import ctypes
 import io
@@ -38,6 +40,20 @@ class HaLstmSeqNet(ctypes.Structure):
 
 class HaLstmSeqBwd(ctypes.Structure):
     _fields_ = [(k, _VP) for k in ("w_hh", "c0", "c", "gates", "d_h", "d_gates")]
+
+
+class HaLstmSeqWgrad(ctypes.Structure):
+    _fields_ = [(k, _VP) for k in ("d_gates", "h", "h0", "d_w_ih", "d_w_hh", "d_b")]
+
+
+WGRAD_BLOCK, WGRAD_CHUNK = 128, 64   # HA_WGRAD_BLOCK, HA_WGRAD_CHUNK of include/hedge_actor.h
+WEIGHT_GRADS = ("torch", "kernel")
+
+
+def _weight_grads_mode(mode):
+    if mode not in WEIGHT_GRADS:
+        raise ValueError(f"weight_grads must be one of {WEIGHT_GRADS}, not {mode!r}")
+    return mode
 
 
 def _check(lib, status, what):
@@ -148,6 +164,44 @@ def lstm_seq_backward(episode_starts, nets, host=None):
     return out
 
 
+def lstm_seq_weight_grads(x, episode_starts, nets, host=None):
+    """ha_lstm_seq_weight_grads (contract W1-W4): x [L,B,13], episode_starts [L,B], nets = one or two
+    dicts of d_gates [L,B,4,128], h [L,B,128] (the forward's), h0 [B,128] -> a list of (d_w_ih [512,13],
+    d_w_hh [512,128], d_b [512]) f32 per network; d_b is db_ih and db_hh.  No autograd."""
+    lib = load()
+    dev = x.device
+    host = dev.type == "cpu" if host is None else bool(host)
+    if host != (dev.type == "cpu"):
+        raise ValueError("host=True takes CPU tensors, host=False tensors on a HIP device")
+    if x.dim() != 3 or x.shape[2] != OBS_DIM:
+        raise ValueError(f"x must be [L, B, {OBS_DIM}]")
+    L, B = int(x.shape[0]), int(x.shape[1])
+    x = _f32(x, (L, B, OBS_DIM), "x", dev)
+    es = _starts(episode_starts, L, B, dev)
+    n = len(nets)
+    arr = (HaLstmSeqWgrad * max(n, 1))()
+    shapes = dict(d_gates=(L, B, 4, HIDDEN), h=(L, B, HIDDEN), h0=(B, HIDDEN))
+    keep, out = [x, es], []
+    for k, net in enumerate(nets[:2]):
+        for name, shape in shapes.items():
+            t = _f32(net[name], shape, name, dev)
+            keep.append(t)
+            setattr(arr[k], name, t.data_ptr())
+        g = (torch.empty((4 * HIDDEN, OBS_DIM), dtype=torch.float32, device=dev),
+             torch.empty((4 * HIDDEN, HIDDEN), dtype=torch.float32, device=dev),
+             torch.empty(4 * HIDDEN, dtype=torch.float32, device=dev))
+        arr[k].d_w_ih, arr[k].d_w_hh, arr[k].d_b = (t.data_ptr() for t in g)
+        out.append(g)
+    if host:
+        st = lib.ha_host_lstm_seq_weight_grads(n, L, B, x.data_ptr(), es.data_ptr(), arr)
+    else:
+        with torch.cuda.device(dev):
+            ws = torch.empty(lib.ha_lstm_seq_weight_grads_workspace_bytes(n, L, B), dtype=torch.uint8, device=dev)
+            st = lib.ha_lstm_seq_weight_grads(n, L, B, x.data_ptr(), es.data_ptr(), arr, ws.data_ptr(), _stream(dev))
+    _check(lib, st, "ha_lstm_seq_weight_grads")
+    return out
+
+
 def weight_grads(d_gates, x, h, h0, episode_starts, rows=1 << 18, block=128):
     """The LSTM's weight gradients from d_gates [L,B,4,128], as f64 tensors: dW_ih = d_gates^T x,
     dW_hh = d_gates^T h_prev, db_ih = db_hh = sum d_gates, with h_prev = h shifted by one step, h0 in
@@ -190,7 +244,7 @@ class _LstmSeq(torch.autograd.Function):
         for net, (h, c, gates) in zip(nets, out):
             saved += [net["h0"], net["c0"], net["w_hh"], h, c, gates]
         ctx.save_for_backward(*saved)
-        ctx.host, ctx.n = host, n
+        ctx.host, ctx.n, ctx.weight_grads = host, n, "torch"
         return tuple(h for h, _, _ in out)
 
     @staticmethod
@@ -204,25 +258,48 @@ class _LstmSeq(torch.autograd.Function):
             nets.append(dict(w_hh=w_hh, c0=c0, c=c, gates=gates, d_h=d))
         d_gates = lstm_seq_backward(es, nets, host=ctx.host)
         grads = [None, None, None]
+        if ctx.weight_grads == "kernel":   # both networks in one call
+            wg = lstm_seq_weight_grads(x, es, [dict(d_gates=dg, h=h, h0=h0)
+                                               for (h0, c0, w_hh, h, c, gates), dg in zip(per, d_gates)], host=ctx.host)
+            for d_w_ih, d_w_hh, d_b in wg:
+                grads += [None, None, d_w_ih, d_w_hh, d_b, d_b.clone()]
+            return tuple(grads)
         for (h0, c0, w_hh, h, c, gates), dg in zip(per, d_gates):
             grads += [None, None, *(g.to(torch.float32) for g in weight_grads(dg, x, h, h0, es))]
         return tuple(grads)
 
 
-def lstm_sequence(x, episode_starts, h0, c0, w_ih, w_hh, b_ih, b_hh, host=None):
+class _LstmSeqKernel(_LstmSeq):
+    """_LstmSeq with the weight gradients from ha_lstm_seq_weight_grads (weight_grads="kernel")."""
+
+    @staticmethod
+    def forward(ctx, host, x, episode_starts, *tensors):
+        out = _LstmSeq.forward(ctx, host, x, episode_starts, *tensors)
+        ctx.weight_grads = "kernel"
+        return out
+
+
+def _seq_op(weight_grads):
+    return _LstmSeqKernel if _weight_grads_mode(weight_grads) == "kernel" else _LstmSeq
+
+
+def lstm_sequence(x, episode_starts, h0, c0, w_ih, w_hh, b_ih, b_hh, host=None, weight_grads="torch"):
     """The LSTM (13 -> 128, one layer, torch's gate order) over x [L,B,13] from (h0, c0) [B,128], the
     state zeroed before every step where episode_starts [L,B] is set -> h [L,B,128], differentiable
     in the four weight tensors.  x, h0 and c0 receive no gradient (SB3 stores them as constants).
-    One forward and one backward launch; host=True (default for CPU tensors) runs the host build."""
+    One forward and one backward launch; host=True (default for CPU tensors) runs the host build.
+    weight_grads: "torch" forms the weight gradients from d_gates with train.weight_grads (blocked
+    f32 GEMMs added in f64), "kernel" with ha_lstm_seq_weight_grads (contract W1-W4: the same bits on
+    the device and on the host build)."""
     host = x.device.type == "cpu" if host is None else bool(host)
-    return _LstmSeq.apply(host, x, episode_starts, h0, c0, w_ih, w_hh, b_ih, b_hh)[0]
+    return _seq_op(weight_grads).apply(host, x, episode_starts, h0, c0, w_ih, w_hh, b_ih, b_hh)[0]
 
 
-def lstm_sequence_pair(x, episode_starts, actor, critic, host=None):
+def lstm_sequence_pair(x, episode_starts, actor, critic, host=None, weight_grads="torch"):
     """lstm_sequence for actor and critic in one launch each way: `actor`, `critic` are the NET_INPUTS
     tuples (h0, c0, w_ih, w_hh, b_ih, b_hh) -> (h_pi, h_vf)."""
     host = x.device.type == "cpu" if host is None else bool(host)
-    return _LstmSeq.apply(host, x, episode_starts, *actor, *critic)
+    return _seq_op(weight_grads).apply(host, x, episode_starts, *actor, *critic)
 
 
 # --------------------------------------------------------------------------- the policy as a torch module
@@ -254,10 +331,13 @@ class RecurrentPPOModule(torch.nn.Module):
     net_arch 64-64, a state-independent log_std) with its 21 tensors under the checkpoint's own names:
     state_dict() feeds RecurrentPolicy.load_state_dict as it is.  activation: "tanh" (SB3's default)
     or "relu".  obs_mean / obs_var: the statistics a RecurrentPolicy applies to raw obs (contract step
-    2); leave them out when the buffer holds normalised obs (a DeviceVecNormalize env)."""
+    2); leave them out when the buffer holds normalised obs (a DeviceVecNormalize env).  weight_grads:
+    lstm_sequence's keyword, passed on by evaluate_actions."""
 
-    def __init__(self, activation="tanh", obs_mean=None, obs_var=None, clip_obs=10.0, epsilon=1e-8):
+    def __init__(self, activation="tanh", obs_mean=None, obs_var=None, clip_obs=10.0, epsilon=1e-8,
+                 weight_grads="torch"):
         super().__init__()
+        self.weight_grads = _weight_grads_mode(weight_grads)
         acts = {"tanh": torch.nn.Tanh, "relu": torch.nn.ReLU}
         if activation not in acts:
             raise ValueError(f"activation must be one of {sorted(acts)}, not {activation!r}")
@@ -295,11 +375,11 @@ class RecurrentPPOModule(torch.nn.Module):
         return cls.from_state_dict(sd, normalization=normalization, **kw)
 
     @classmethod
-    def from_policy(cls, policy, device=None):
+    def from_policy(cls, policy, device=None, weight_grads="torch"):
         """The tensors, activation and statistics of an agent.RecurrentPolicy, on its device."""
         a = policy._arrays
         m = cls(activation=policy.activation, obs_mean=a.get("obs_mean"), obs_var=a.get("obs_var"),
-                clip_obs=policy.clip_obs, epsilon=policy.epsilon)
+                clip_obs=policy.clip_obs, epsilon=policy.epsilon, weight_grads=weight_grads)
         m.load_state_dict({k: torch.from_numpy(a[f].copy()) for k, f, _ in POLICY_KEYS})
         return m.to(policy.device_name if device is None else device)
 
@@ -326,7 +406,8 @@ class RecurrentPPOModule(torch.nn.Module):
         (values, log_prob, entropy), each [L,B]."""
         x = self.normalize_obs(obs)
         h_pi, h_vf = lstm_sequence_pair(x, episode_starts, (states0[0], states0[1], *self.lstm_actor.tensors()),
-                                        (states0[2], states0[3], *self.lstm_critic.tensors()), host=host)
+                                        (states0[2], states0[3], *self.lstm_critic.tensors()), host=host,
+                                        weight_grads=self.weight_grads)
         return self.heads(h_pi, h_vf, actions)
 
 

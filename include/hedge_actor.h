@@ -4,7 +4,8 @@
  * Linear 2) evaluated for N device-resident envs in one HIP kernel on MI355X (gfx950), the
  * per-episode sums of a closed-loop evaluation around he_step, and the training side: actor,
  * critic, action sampling and log-probability of a rollout step in one launch, GAE, and for the
- * PPO update both LSTMs over a stored sequence with per-step resets, forward and backward.
+ * PPO update both LSTMs over a stored sequence with per-step resets, forward and backward, and
+ * their weight gradients.
  *
  * Conventions (as hedge_env.h): plain C types, every entry point returns an ha_status (the
  * he_status values), the last failure's message is ha_last_error(handle), no C++ exception
@@ -82,8 +83,24 @@
  *   B4. dh_rec[j] = episode_starts[t] ? 0 : the k-ordered f32 fmaf chain from 0 over
  *       u = 0 .. 511 (torch's gate rows: i, f, g, o blocks of 128) of d_gates[t][u] w_hh[u][j].
  *       v_mfma_f32_32x32x2_f32 over K = 512 in one accumulator computes exactly this chain.
- *   The weight gradients are sums over the L B rows of d_gates (dW_ih = d_gates^T x,
- *   dW_hh = d_gates^T h_prev, db_ih = db_hh = sum d_gates): GEMMs, left to the caller.
+ *
+ * The weight gradients (ha_lstm_seq_weight_grads: dW_ih = d_gates^T x, dW_hh = d_gates^T h_prev,
+ * db_ih = db_hh = sum d_gates, sums over the L B rows of d_gates).  Per network, rows r = t B + e
+ * for r in [0, R), R = L B; dg[r][u] = d_gates[t][e][u], u = 0 .. 511 in torch's row order;
+ * z[r][k], k = 0 .. 141: x[t][e][k] for k < 13; h_prev[t][e][k - 13] for 13 <= k < 141, with
+ * h_prev = 0 where episode_starts[t][e], else h[t-1][e] (h0[e] at t = 0); 1.0 at k = 141 (the bias
+ * column).
+ *   W1. block sum: the rows are cut into blocks of HA_WGRAD_BLOCK consecutive rows.  s_b[u][k] is
+ *       the f32 fmaf chain from +0 over the block's rows in ascending order,
+ *       s = fmaf(dg[r][u], z[r][k], s); a short last block is continued with terms
+ *       fmaf(+0, +0, s) up to the full block (part of the contract: both builds may pad).
+ *       v_mfma_f32_32x32x2_f32 with the row index as its k computes exactly this chain.
+ *   W2. chunk sum: HA_WGRAD_CHUNK consecutive blocks form a chunk; p_c[u][k] is the f64 sum from
+ *       0.0 of f64(s_b[u][k]) over the chunk's blocks in ascending order.
+ *   W3. total[u][k] is the f64 sum from 0.0 of p_c[u][k] over ascending chunks.
+ *   W4. outputs, each rounded once from f64 to f32: d_w_ih[u][k] = total[u][k] for k < 13,
+ *       d_w_hh[u][j] = total[u][13 + j], d_b[u] = total[u][141] (the value of db_ih and db_hh).
+ *   Nothing in W1-W4 depends on the grid, the CU count or the number of networks per call.
  */
 #ifndef HEDGE_ACTOR_H
 #define HEDGE_ACTOR_H
@@ -311,6 +328,40 @@ ha_status ha_host_lstm_seq_forward(int64_t n_nets, int64_t L, int64_t B, const f
                                    const uint8_t* episode_starts, const ha_lstm_seq_net* nets);
 ha_status ha_host_lstm_seq_backward(int64_t n_nets, int64_t L, int64_t B, const uint8_t* episode_starts,
                                     const ha_lstm_seq_bwd* nets);
+
+/* ---- the LSTM's weight gradients from d_gates (W1-W4) ---- */
+#define HA_WGRAD_BLOCK 128 /* rows of one f32 fmaf chain (W1) */
+#define HA_WGRAD_CHUNK 64  /* blocks of one f64 partial (W2): 8,192 rows a chunk */
+
+/* One network of ha_lstm_seq_weight_grads: the backward's d_gates [L][B][4][128], the forward's h
+ * [L][B][128] and its h0 [B][128] in; d_w_ih [512][13], d_w_hh [512][128], d_b [512] out. */
+typedef struct ha_lstm_seq_wgrad {
+    const float* d_gates;
+    const float* h;
+    const float* h0;
+    float* d_w_ih;
+    float* d_w_hh;
+    float* d_b;
+} ha_lstm_seq_wgrad;
+
+/* Bytes of the workspace ha_lstm_seq_weight_grads takes: the chunks' f64 partials p_c, [512][142]
+ * per chunk and network.  0 for n_nets other than 1 or 2 or a shape the call refuses.  The
+ * workspace carries nothing from call to call. */
+size_t ha_lstm_seq_weight_grads_workspace_bytes(int64_t n_nets, int64_t L, int64_t B);
+
+/* W1-W4 for n_nets = 1 or 2 networks over the same x [L][B][13] and episode_starts [L][B] u8: two
+ * launches, one workgroup per (chunk, 128 gate rows, network) forming p_c, then one thread per
+ * output adding the chunks in order.  DEVICE pointers, 16-byte aligned but for x (52-byte rows);
+ * stream-ordered, no host synchronisation, no allocation.  The checks of ha_lstm_seq_forward, made
+ * before anything is launched; also HE_ESHAPE when L B has more than 2^31 - 1 chunks.  The message
+ * is ha_policy_last_error(NULL). */
+ha_status ha_lstm_seq_weight_grads(int64_t n_nets, int64_t L, int64_t B, const float* x,
+                                   const uint8_t* episode_starts, const ha_lstm_seq_wgrad* nets, void* workspace,
+                                   void* stream);
+
+/* The same arithmetic on the host, HOST pointers (no alignment asked), no workspace. */
+ha_status ha_host_lstm_seq_weight_grads(int64_t n_nets, int64_t L, int64_t B, const float* x,
+                                        const uint8_t* episode_starts, const ha_lstm_seq_wgrad* nets);
 
 #ifdef __cplusplus
 }

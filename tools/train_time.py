@@ -5,7 +5,14 @@ _process_sequence loop of one cell per time step with the state zeroed at episod
 autograd, f32.  And one ppo_update epoch over a buffer of the first shape.  HIP events around each
 call, warm-up first, the median.
 
-    python tools/train_time.py [--reps R] [--out FILE.jsonl] [--shapes L,B ...]
+    python tools/train_time.py [--reps R] [--out FILE.jsonl] [--shapes L,B ...] [--weight-grads torch|kernel|both]
+
+--weight-grads torch (the default) times lstm_sequence_pair as it is called by default, its weight
+gradients from train.weight_grads.  kernel times forward plus backward with weight_grads="kernel", and
+ha_lstm_seq_weight_grads alone on the backward's d_gates: per network and for the pair in one call,
+beside its two floors (2 x 512 x 142 FLOP a row at the 155 TFLOP/s f32-MFMA rate; 2,048 + 512 + 52 + 1
+bytes a row at the 6.29 TB/s copy ceiling).  both adds train.weight_grads alone on the same tensors,
+the baseline, in the same process.
 
 Default shapes: L = 256 with B = 4,096 and 16,384 (the largest power of two at which the all-torch
 composition's saved activations, about 8 KB per step, env and network, still fit beside the kernel's
@@ -28,6 +35,8 @@ from cantorrl_amd.agent import POLICY_KEYS  # noqa: E402
 from cantorrl_amd.collect import RolloutBuffer  # noqa: E402
 
 FLOP_FWD, FLOP_BWD = 2 * 512 * 141, 2 * 512 * 128
+FLOP_WGRAD, BYTES_WGRAD = 2 * 512 * 142, 2048 + 512 + 52 + 1   # per row and network
+PEAK_F32_MFMA, COPY_CEILING = 155e12, 6.29e12                 # FLOP/s, B/s (measured, MI355X)
 DEV = "cuda:0"
 
 
@@ -51,7 +60,31 @@ def module(rng):
     return m.to(DEV)
 
 
-def measure(L, B, reps):
+def measure_weight_grads(r, x, es, nets, d_h, reps, mode):
+    """The weight gradients alone, on the d_gates of the backward kernel."""
+    L, B = es.shape
+    with torch.no_grad():
+        fwd = train.lstm_seq_forward(x, es, [dict(zip(train.NET_INPUTS, n)) for n in nets])
+        bwd = [dict(w_hh=n[3], c0=n[1], c=o[1], gates=o[2], d_h=d) for n, o, d in zip(nets, fwd, d_h)]
+        d_gates = train.lstm_seq_backward(es, bwd)
+    wn = [dict(d_gates=dg, h=o[0], h0=n[0]) for dg, o, n in zip(d_gates, fwd, nets)]
+    rows = L * B
+    r["wgrad_kernel_net_us"] = [round(median_us(lambda k=k: train.lstm_seq_weight_grads(x, es, [wn[k]]), reps, 3), 1)
+                                for k in range(2)]
+    r["wgrad_kernel_pair_us"] = round(median_us(lambda: train.lstm_seq_weight_grads(x, es, wn), reps, 3), 1)
+    r["wgrad_floor_flop_us"] = round(rows * FLOP_WGRAD / PEAK_F32_MFMA * 1e6, 1)
+    r["wgrad_floor_bytes_us"] = round(rows * BYTES_WGRAD / COPY_CEILING * 1e6, 1)
+    per_net = r["wgrad_kernel_pair_us"] / 2
+    r["wgrad_kernel_frac_of_flop_floor"] = round(r["wgrad_floor_flop_us"] / per_net, 3)
+    r["wgrad_kernel_frac_of_bytes_floor"] = round(r["wgrad_floor_bytes_us"] / per_net, 3)
+    r["wgrad_kernel_tflops"] = round(rows * FLOP_WGRAD / per_net / 1e6, 2)
+    if mode == "both":
+        r["wgrad_torch_net_us"] = [round(median_us(lambda k=k: train.weight_grads(d_gates[k], x, fwd[k][0], nets[k][0], es),
+                                                   reps, 3), 1) for k in range(2)]
+        r["wgrad_speedup_per_net"] = round(sum(r["wgrad_torch_net_us"]) / r["wgrad_kernel_pair_us"], 2)
+
+
+def measure(L, B, reps, mode="torch"):
     rng = np.random.default_rng(0)
     m = module(rng)
     g = torch.Generator(device=DEV).manual_seed(1)
@@ -80,9 +113,20 @@ def measure(L, B, reps):
         h = [torch_lstm_loop(x, es, *n) for n in nets]
         torch.autograd.backward(h, d_h)
 
+    def kernel_both_wgrad():
+        m.zero_grad(set_to_none=True)
+        h = train.lstm_sequence_pair(x, es, *nets, weight_grads="kernel")
+        torch.autograd.backward(h, d_h)
+
     r = dict(L=L, B=B, reps=reps, device=torch.cuda.get_device_name(0))
     r["kernel_fwd_us"] = round(median_us(kernel_fwd, reps, 3), 1)
     r["kernel_fwd_bwd_us"] = round(median_us(kernel_both, reps, 3), 1)
+    if mode != "torch":
+        r["weight_grads"] = mode
+        r["kernel_fwd_bwd_wgrad_kernel_us"] = round(median_us(kernel_both_wgrad, reps, 3), 1)
+        measure_weight_grads(r, x, es, nets, d_h, reps, mode)
+    if mode == "kernel":   # the all-torch composition is the default mode's comparison
+        return r, m
     treps = reps if L * B <= 2 ** 20 else max(reps // 10, 3)   # the loop is 256 x ~40 launches a pass
     r["torch_fwd_us"] = round(median_us(torch_fwd, treps, 2), 1)
     r["torch_fwd_bwd_us"] = round(median_us(torch_both, treps, 2), 1)
@@ -112,12 +156,13 @@ def main():
     ap.add_argument("--shapes", nargs="*", default=["256,4096", "256,16384", "32,2"])
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--out")
+    ap.add_argument("--weight-grads", choices=("torch", "kernel", "both"), default="torch")
     a = ap.parse_args()
     lines = []
     for k, s in enumerate(a.shapes):
         L, B = (int(v) for v in s.split(","))
-        r, m = measure(L, B, a.reps)
-        if k == 0:
+        r, m = measure(L, B, a.reps, a.weight_grads)
+        if k == 0 and a.weight_grads != "kernel":
             r.update(measure_update(m, L, B, max(B // 4, 1), max(a.reps // 5, 3)))
         del m
         torch.cuda.empty_cache()
