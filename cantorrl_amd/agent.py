@@ -92,6 +92,7 @@ class HaPolicyWeights(ctypes.Structure):
 
 
 _lib_ha = None
+_torch = None   # the torch module, from the first device handle on (this module imports without torch)
 
 
 def load(path=LIB_PATH):
@@ -143,38 +144,63 @@ def load(path=LIB_PATH):
     return lib
 
 
-def _check(lib, handle, status, what):
+def _check(lib, status, what, handle=None, last_error="ha_last_error"):
+    """Raise for a status other than HE_OK with the message of `handle` (None: the calling thread's,
+    which either getter returns); last_error names the getter of the handle's kind."""
     if status != _lib.HE_OK:
-        msg = (lib.ha_last_error(handle) or b"").decode()
+        msg = (getattr(lib, last_error)(handle) or b"").decode()
         if status in (_lib.HE_ESHAPE, _lib.HE_EINVAL):
             raise ValueError(f"{what}: {msg}")
         raise _lib.HedgeEnvError(f"{what} failed (status {status}): {msg}")
 
 
-def _layer_indices(sd, prefix):
-    return sorted({k[len(prefix):].split("_l")[-1] for k in sd if k.startswith(prefix)})
-
-
-def weights_from_state_dict(sd):
-    """The 11 actor tensors of an SB3 RecurrentPPO state dict as contiguous f32 arrays, keyed by
-    ha_weights field; ValueError for any architecture but 13 -> LSTM 128 x 1 -> 64 -> 64 -> 2."""
-    layers = _layer_indices(sd, "lstm_actor.weight_ih")
+def _net_from_state_dict(sd, lstm_prefix, mlp_prefix, keys, what):
+    """One network (`what`: "actor" or "critic") of an SB3 RecurrentPPO state dict: the tensors of
+    `keys` as contiguous f32 arrays by field; ValueError unless it is one LSTM layer and 64 -> 64."""
+    stem = lstm_prefix + ".weight_ih"
+    layers = sorted({k[len(stem):].split("_l")[-1] for k in sd if k.startswith(stem)})
     if layers != ["0"]:
-        raise ValueError(f"lstm_actor has layers {layers}: only n_lstm_layers=1 is built")
-    extra = sorted(k for k in sd if k.startswith("mlp_extractor.policy_net.") and k.split(".")[2] not in ("0", "2"))
+        raise ValueError(f"{lstm_prefix} has layers {layers}: only n_lstm_layers=1 is built")
+    extra = sorted(k for k in sd if k.startswith(mlp_prefix) and k.split(".")[2] not in ("0", "2"))
     if extra:
-        raise ValueError(f"policy_net has layers beyond 64 -> 64: {extra}")
+        raise ValueError(f"{mlp_prefix.split('.')[1]} has layers beyond 64 -> 64: {extra}")
     out = {}
-    for key, field, shape in ACTOR_KEYS:
+    for key, field, shape in keys:
         if key not in sd:
             raise ValueError(f"state dict has no {key!r}")
         t = sd[key]
         a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
         if tuple(a.shape) != shape:
-            raise ValueError(f"{key} has shape {tuple(a.shape)}, this actor is built for {shape} "
-                             "(obs 13, lstm_hidden_size 128, net_arch 64-64, 2 actions)")
+            raise ValueError(f"{key} has shape {tuple(a.shape)}, this {what} is built for {shape} (obs 13, "
+                             f"lstm_hidden_size 128, net_arch 64-64, {'2 actions' if what == 'actor' else '1 value'})")
         out[field] = np.ascontiguousarray(a, dtype=np.float32)
     return out
+
+
+def weights_from_state_dict(sd):
+    """The 11 actor tensors of an SB3 RecurrentPPO state dict as contiguous f32 arrays, keyed by
+    ha_weights field; ValueError for any architecture but 13 -> LSTM 128 x 1 -> 64 -> 64 -> 2."""
+    return _net_from_state_dict(sd, "lstm_actor", "mlp_extractor.policy_net.", ACTOR_KEYS, "actor")
+
+
+def policy_weights_from_state_dict(sd):
+    """The actor's 11 and the critic's 10 tensors of an SB3 RecurrentPPO state dict, keyed by
+    ha_policy_weights field.  ValueError unless the critic has its own LSTM (sb3_contrib's default,
+    enable_critic_lstm=True and shared_lstm=False) of the actor's shape."""
+    out = weights_from_state_dict(sd)
+    if not any(k.startswith("lstm_critic.") for k in sd):
+        raise ValueError("state dict has no lstm_critic.*: RecurrentPolicy is built for a critic with its own LSTM "
+                         "(enable_critic_lstm=True, shared_lstm=False); shared_lstm=True and a critic without an "
+                         "LSTM (enable_critic_lstm=False) are not")
+    out.update(_net_from_state_dict(sd, "lstm_critic", "mlp_extractor.value_net.", CRITIC_KEYS, "critic"))
+    return out
+
+
+def _read_sb3_zip(path):
+    """The state dict of an SB3 `model.save()` zip: its policy.pth is a plain torch state dict."""
+    import torch
+    with zipfile.ZipFile(path) as z:
+        return torch.load(io.BytesIO(z.read("policy.pth")), map_location="cpu", weights_only=True)
 
 
 def _normalization(norm):
@@ -190,7 +216,139 @@ def _normalization(norm):
     return rms.mean, rms.var, {"clip_obs": float(norm.clip_obs), "epsilon": float(norm.epsilon)}
 
 
-class RecurrentActor:
+class _Recurrent:
+    """What RecurrentActor and RecurrentPolicy share: the weights struct (self._w, pointing into
+    self._arrays) from tensors, statistics and activation, the loaders, the device handle made with
+    the first device call, and the validation of a step's inputs.  A subclass names its struct, key
+    table, state attributes and entry points, and adds what differs."""
+
+    _struct = _abi = _keys = _fields_of = None   # ctypes struct, its abi_version, key table, state dict -> fields
+    _states = ()                                 # the attributes holding [n, ...] device tensors
+    _create = _destroy = _last_error = None      # entry-point names
+
+    def __init__(self, weights, obs_mean, obs_var, clip_obs, epsilon, activation, device):
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}, not {activation!r}")
+        if (obs_mean is None) != (obs_var is None):
+            raise ValueError("obs_mean and obs_var come together")
+        self.lib = load()
+        self._arrays = {}
+        w = self._w = self._struct()
+        w.abi_version = self._abi
+        w.obs_dim, w.hidden, w.n_lstm_layers, w.mlp_width, w.act_dim = OBS_DIM, HIDDEN, 1, MLP, ACT_DIM
+        w.activation = ACTIVATIONS[activation]
+        w.has_clip = 0 if clip_obs is None else 1
+        w.clip_obs = 0.0 if clip_obs is None else float(clip_obs)
+        w.epsilon = float(epsilon)
+        self._set_tensors(weights)
+        if obs_mean is not None:
+            for name, v in (("obs_mean", obs_mean), ("obs_var", obs_var)):
+                a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
+                if a.shape != (OBS_DIM,):
+                    raise ValueError(f"{name} has {a.size} entries, the obs has {OBS_DIM}")
+                self._arrays[name] = a
+                setattr(w, name, a.ctypes.data_as(_D))
+        self.activation = activation
+        self.clip_obs, self.epsilon = clip_obs, float(epsilon)
+        self.device_name = device
+        self._h = None          # the library's handle, made with the first device call
+        self.device = None
+        for k in self._states:  # [n, ...] device tensors (reset_states)
+            setattr(self, k, None)
+
+    def _set_tensors(self, weights):
+        if any("." in k for k in weights):
+            weights = self._fields_of(weights)
+        arrays = {}
+        for _, field, shape in self._keys:
+            a = np.ascontiguousarray(weights[field], dtype=np.float32)
+            if a.shape != shape:
+                raise ValueError(f"{field} has shape {a.shape}, expected {shape}")
+            arrays[field] = a
+        self._arrays.update(arrays)   # the struct points into these: they live as long as it does
+        for field, a in arrays.items():
+            setattr(self._w, field, a.ctypes.data_as(_F))
+
+    # ------------------------------------------------------------------ loaders
+    @classmethod
+    def from_state_dict(cls, sd, normalization=None, **kw):
+        mean, var, over = _normalization(normalization)
+        return cls(cls._fields_of(sd), obs_mean=mean, obs_var=var, **dict(over, **kw))
+
+    @classmethod
+    def from_sb3_zip(cls, path, normalization=None, **kw):
+        """An SB3 `model.save()` zip: its policy.pth is a plain torch state dict."""
+        return cls.from_state_dict(_read_sb3_zip(path), normalization=normalization, **kw)
+
+    # ------------------------------------------------------------------ device
+    def _handle(self):
+        if self._h is None:
+            global _torch
+            import torch
+            _torch = torch
+            dev = torch.device(self.device_name)
+            if dev.type != "cuda" or not torch.cuda.is_available():
+                raise _lib.HedgeEnvError(f"{type(self).__name__}.step runs on a HIP device (cuda:N); "
+                                         "host_step is the CPU build")
+            dev = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
+            h = ctypes.c_void_p()
+            with torch.cuda.device(dev):
+                st = getattr(self.lib, self._create)(ctypes.byref(self._w), ctypes.byref(h))
+                _check(self.lib, st, self._create, None, self._last_error)
+            self._h, self.device = h, dev
+        return self._h
+
+    def _stream(self):
+        from .vec_env import _raw_stream
+        return _raw_stream(self.device.index)
+
+    def _begin_step(self, obs, episode_start):
+        """The head of a device step: the handle, and obs [n,13] f32 and episode_start [n] u8 / bool
+        device tensors checked -> (handle, n, episode_start as uint8).  One call a step: at small env
+        counts the step is bound by this Python."""
+        h = self._h if self._h is not None else self._handle()
+        torch = _torch
+        n = int(obs.shape[0])
+        if obs.dtype != torch.float32 or not obs.is_contiguous() or obs.device != self.device or obs.shape[1] != OBS_DIM:
+            raise ValueError(f"obs must be a contiguous float32 [n, {OBS_DIM}] tensor on {self.device}")
+        if episode_start.dtype == torch.bool:
+            episode_start = episode_start.view(torch.uint8)
+        if episode_start.dtype != torch.uint8 or episode_start.numel() != n or not episode_start.is_contiguous():
+            raise ValueError("episode_start must be a contiguous uint8 / bool [n] tensor")
+        return h, n, episode_start
+
+    @staticmethod
+    def _host_inputs(obs, episode_start, names, states):
+        """host_step's NumPy inputs: obs [n,13] and episode_start [n] converted, `states` (C-contiguous
+        float32 [n,128] arrays, updated in place by the call) checked -> (obs, episode_start, n)."""
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        n = obs.shape[0]
+        es = np.ascontiguousarray(np.asarray(episode_start).reshape(-1), dtype=np.uint8)
+        if obs.shape != (n, OBS_DIM) or es.shape != (n,):
+            raise ValueError(f"obs must be [n, {OBS_DIM}] and episode_start [n]")
+        for name, a in zip(names, states):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous
+                    and a.shape == (n, HIDDEN)):
+                raise ValueError(f"{name} must be a C-contiguous float32 [{n}, {HIDDEN}] array")
+        return obs, es, n
+
+    def close(self):
+        if self._h is not None:
+            import torch
+            torch.cuda.synchronize(self.device)
+            getattr(self.lib, self._destroy)(self._h)
+            self._h = None
+        for k in self._states:
+            setattr(self, k, None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RecurrentActor(_Recurrent):
     """The deterministic actor of a RecurrentPPO checkpoint.
 
     weights: {field: array} (weights_from_state_dict) or a state dict.  obs_mean / obs_var (f64
@@ -199,75 +357,17 @@ class RecurrentActor:
     eval output).  activation: the MLP's ("tanh": SB3's default, "relu": model_wrapper.py);
     squash: "clip" (SB3 predict) or "tanh" (model_wrapper.py)."""
 
+    _struct, _abi, _keys, _fields_of = HaWeights, HA_ABI_VERSION, ACTOR_KEYS, staticmethod(weights_from_state_dict)
+    _states = ("h", "c", "_sums")   # h, c [n, 128]; the episode sums
+    _create, _destroy, _last_error = "ha_create", "ha_destroy", "ha_last_error"
+
     def __init__(self, weights, obs_mean=None, obs_var=None, clip_obs=10.0, epsilon=1e-8, activation="tanh",
                  squash="clip", device="cuda:0"):
-        if any("." in k for k in weights):
-            weights = weights_from_state_dict(weights)
-        if activation not in ACTIVATIONS:
-            raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}, not {activation!r}")
         if squash not in SQUASHES:
             raise ValueError(f"squash must be one of {sorted(SQUASHES)}, not {squash!r}")
-        self.lib = load()
-        self._arrays = {}
-        for _, field, shape in ACTOR_KEYS:
-            a = np.ascontiguousarray(weights[field], dtype=np.float32)
-            if a.shape != shape:
-                raise ValueError(f"{field} has shape {a.shape}, expected {shape}")
-            self._arrays[field] = a
-        if (obs_mean is None) != (obs_var is None):
-            raise ValueError("obs_mean and obs_var come together")
-        w = HaWeights()
-        w.abi_version = HA_ABI_VERSION
-        w.obs_dim, w.hidden, w.n_lstm_layers, w.mlp_width, w.act_dim = OBS_DIM, HIDDEN, 1, MLP, ACT_DIM
-        w.activation, w.squash = ACTIVATIONS[activation], SQUASHES[squash]
-        w.has_clip = 0 if clip_obs is None else 1
-        w.clip_obs = 0.0 if clip_obs is None else float(clip_obs)
-        w.epsilon = float(epsilon)
-        for _, field, _s in ACTOR_KEYS:
-            setattr(w, field, self._arrays[field].ctypes.data_as(_F))
-        if obs_mean is not None:
-            for name, v in (("obs_mean", obs_mean), ("obs_var", obs_var)):
-                a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
-                if a.shape != (OBS_DIM,):
-                    raise ValueError(f"{name} has {a.size} entries, the obs has {OBS_DIM}")
-                self._arrays[name] = a
-                setattr(w, name, a.ctypes.data_as(_D))
-        self._w = w
-        self.activation, self.squash = activation, squash
-        self.clip_obs, self.epsilon = clip_obs, float(epsilon)
-        self.device_name = device
-        self._h = None          # ha_actor*, made with the first device call
-        self.device = None
-        self.h = self.c = None  # [n, 128] device tensors (reset_states)
-        self._sums = None
-
-    # ------------------------------------------------------------------ loaders
-    @classmethod
-    def from_state_dict(cls, sd, normalization=None, **kw):
-        mean, var, over = _normalization(normalization)
-        return cls(weights_from_state_dict(sd), obs_mean=mean, obs_var=var, **dict(over, **kw))
-
-    @classmethod
-    def from_sb3_zip(cls, path, normalization=None, **kw):
-        """An SB3 `model.save()` zip: its policy.pth is a plain torch state dict."""
-        import torch
-        with zipfile.ZipFile(path) as z:
-            sd = torch.load(io.BytesIO(z.read("policy.pth")), map_location="cpu", weights_only=True)
-        return cls.from_state_dict(sd, normalization=normalization, **kw)
-
-    # ------------------------------------------------------------------ device
-    def _handle(self):
-        if self._h is None:
-            import torch
-            dev = torch.device(self.device_name)
-            if dev.type != "cuda" or not torch.cuda.is_available():
-                raise _lib.HedgeEnvError("RecurrentActor.step runs on a HIP device (cuda:N); host_step is the CPU build")
-            dev = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
-            h = ctypes.c_void_p()
-            with torch.cuda.device(dev):
-                _check(self.lib, None, self.lib.ha_create(ctypes.byref(self._w), ctypes.byref(h)), "ha_create")
-            self._h, self.device = h, dev
-        return self._h
+        super().__init__(weights, obs_mean, obs_var, clip_obs, epsilon, activation, device)
+        self._w.squash = SQUASHES[squash]
+        self.squash = squash
 
     def reset_states(self, n_envs):
         """Zero h, c (and the episode sums) for n_envs envs."""
@@ -284,24 +384,13 @@ class RecurrentActor:
             self._sums.zero_()
         return self.h, self.c
 
-    def _stream(self):
-        from .vec_env import _raw_stream
-        return _raw_stream(self.device.index)
-
     def step(self, obs, episode_start, out=None, mean_out=None, obs_norm_out=None):
         """obs [n,13] f32, episode_start [n] u8 / bool device tensors -> actions [n,2]; h, c are
         updated in place.  Enqueued on the current stream, no host sync."""
         import torch
-        h = self._handle()
-        n = int(obs.shape[0])
+        h, n, episode_start = self._begin_step(obs, episode_start)
         if self.h is None or self.h.shape[0] != n:
             self.reset_states(n)
-        if obs.dtype != torch.float32 or not obs.is_contiguous() or obs.device != self.device or obs.shape[1] != OBS_DIM:
-            raise ValueError(f"obs must be a contiguous float32 [n, {OBS_DIM}] tensor on {self.device}")
-        if episode_start.dtype == torch.bool:
-            episode_start = episode_start.view(torch.uint8)
-        if episode_start.dtype != torch.uint8 or episode_start.numel() != n or not episode_start.is_contiguous():
-            raise ValueError("episode_start must be a contiguous uint8 / bool [n] tensor")
         if out is None:
             out = torch.empty((n, ACT_DIM), dtype=torch.float32, device=self.device)
         for t, w in ((out, ACT_DIM), (mean_out, ACT_DIM), (obs_norm_out, OBS_DIM)):
@@ -310,7 +399,7 @@ class RecurrentActor:
         st = self.lib.ha_step(h, n, obs.data_ptr(), episode_start.data_ptr(), self.h.data_ptr(), self.c.data_ptr(),
                               out.data_ptr(), None if mean_out is None else mean_out.data_ptr(),
                               None if obs_norm_out is None else obs_norm_out.data_ptr(), self._stream())
-        _check(self.lib, h, st, "ha_step")
+        _check(self.lib, st, "ha_step", h)
         return out
 
     def accumulate(self, info, terminated, records, record_count, env_id_offset=0):
@@ -324,21 +413,13 @@ class RecurrentActor:
         st = self.lib.ha_accumulate(h, n, int(env_id_offset), *cols, terminated.data_ptr(), self._sums.data_ptr(),
                                     None if records is None else records.data_ptr(), cap, record_count.data_ptr(),
                                     self._stream())
-        _check(self.lib, h, st, "ha_accumulate")
+        _check(self.lib, st, "ha_accumulate", h)
 
     # ------------------------------------------------------------------ host
     def host_step(self, obs, episode_start, h, c, mean_out=None, obs_norm_out=None):
         """ha_host_step over NumPy: obs [n,13] f32, episode_start [n], h / c [n,128] f32 C-contiguous
         arrays updated IN PLACE; returns actions [n,2].  The device kernel's arithmetic on the CPU."""
-        obs = np.ascontiguousarray(obs, dtype=np.float32)
-        n = obs.shape[0]
-        es = np.ascontiguousarray(np.asarray(episode_start).reshape(-1), dtype=np.uint8)
-        for name, a in (("h", h), ("c", c)):
-            if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous
-                    and a.shape == (n, HIDDEN)):
-                raise ValueError(f"{name} must be a C-contiguous float32 [{n}, {HIDDEN}] array")
-        if obs.shape != (n, OBS_DIM) or es.shape != (n,):
-            raise ValueError(f"obs must be [n, {OBS_DIM}] and episode_start [n]")
+        obs, es, n = self._host_inputs(obs, episode_start, ("h", "c"), (h, c))
         act = np.empty((n, ACT_DIM), np.float32)
         for a, w in ((mean_out, ACT_DIM), (obs_norm_out, OBS_DIM)):
             if a is not None and not (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (n, w)):
@@ -346,49 +427,8 @@ class RecurrentActor:
         st = self.lib.ha_host_step(ctypes.byref(self._w), n, obs.ctypes.data, es.ctypes.data, h.ctypes.data,
                                    c.ctypes.data, act.ctypes.data, None if mean_out is None else mean_out.ctypes.data,
                                    None if obs_norm_out is None else obs_norm_out.ctypes.data)
-        _check(self.lib, None, st, "ha_host_step")
+        _check(self.lib, st, "ha_host_step")
         return act
-
-    def close(self):
-        if self._h is not None:
-            import torch
-            torch.cuda.synchronize(self.device)
-            self.lib.ha_destroy(self._h)
-            self._h = None
-        self.h = self.c = self._sums = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def policy_weights_from_state_dict(sd):
-    """The actor's 11 and the critic's 10 tensors of an SB3 RecurrentPPO state dict, keyed by
-    ha_policy_weights field.  ValueError unless the critic has its own LSTM (sb3_contrib's default,
-    enable_critic_lstm=True and shared_lstm=False) of the actor's shape."""
-    out = weights_from_state_dict(sd)
-    if not any(k.startswith("lstm_critic.") for k in sd):
-        raise ValueError("state dict has no lstm_critic.*: RecurrentPolicy is built for a critic with its own LSTM "
-                         "(enable_critic_lstm=True, shared_lstm=False); shared_lstm=True and a critic without an "
-                         "LSTM (enable_critic_lstm=False) are not")
-    layers = _layer_indices(sd, "lstm_critic.weight_ih")
-    if layers != ["0"]:
-        raise ValueError(f"lstm_critic has layers {layers}: only n_lstm_layers=1 is built")
-    extra = sorted(k for k in sd if k.startswith("mlp_extractor.value_net.") and k.split(".")[2] not in ("0", "2"))
-    if extra:
-        raise ValueError(f"value_net has layers beyond 64 -> 64: {extra}")
-    for key, field, shape in CRITIC_KEYS:
-        if key not in sd:
-            raise ValueError(f"state dict has no {key!r}")
-        t = sd[key]
-        a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
-        if tuple(a.shape) != shape:
-            raise ValueError(f"{key} has shape {tuple(a.shape)}, this critic is built for {shape} "
-                             "(obs 13, lstm_hidden_size 128, net_arch 64-64, 1 value)")
-        out[field] = np.ascontiguousarray(a, dtype=np.float32)
-    return out
 
 
 STATE_NAMES = ("h_pi", "c_pi", "h_vf", "c_vf")
@@ -398,7 +438,7 @@ STEP_OUTPUTS = (("actions", (ACT_DIM,)), ("env_actions", (ACT_DIM,)), ("values",
 _REQUIRED_OUT = ("actions", "env_actions", "values", "log_probs")
 
 
-class RecurrentPolicy:
+class RecurrentPolicy(_Recurrent):
     """Actor and critic of a RecurrentPPO checkpoint for rollout collection (collect.RolloutCollector):
     per step the sampled action, its clipped form, the value and the log-probability of every env in
     one kernel launch (ha_policy_step), and GAE over the filled buffer (ha_gae).
@@ -408,63 +448,14 @@ class RecurrentPolicy:
     DeviceVecNormalize, whose obs are normalised already.  The four LSTM states live on the device
     as h_pi, c_pi, h_vf, c_vf [n, 128]."""
 
+    _struct, _abi, _keys = HaPolicyWeights, HA_POLICY_ABI_VERSION, POLICY_KEYS
+    _fields_of = staticmethod(policy_weights_from_state_dict)
+    _states = STATE_NAMES
+    _create, _destroy, _last_error = "ha_policy_create", "ha_policy_destroy", "ha_policy_last_error"
+
     def __init__(self, weights, obs_mean=None, obs_var=None, clip_obs=10.0, epsilon=1e-8, activation="tanh",
                  device="cuda:0"):
-        if activation not in ACTIVATIONS:
-            raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}, not {activation!r}")
-        if (obs_mean is None) != (obs_var is None):
-            raise ValueError("obs_mean and obs_var come together")
-        self.lib = load()
-        self._arrays = {}
-        w = HaPolicyWeights()
-        w.abi_version = HA_POLICY_ABI_VERSION
-        w.obs_dim, w.hidden, w.n_lstm_layers, w.mlp_width, w.act_dim = OBS_DIM, HIDDEN, 1, MLP, ACT_DIM
-        w.activation = ACTIVATIONS[activation]
-        w.has_clip = 0 if clip_obs is None else 1
-        w.clip_obs = 0.0 if clip_obs is None else float(clip_obs)
-        w.epsilon = float(epsilon)
-        self._w = w
-        self._set_tensors(weights)
-        if obs_mean is not None:
-            for name, v in (("obs_mean", obs_mean), ("obs_var", obs_var)):
-                a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
-                if a.shape != (OBS_DIM,):
-                    raise ValueError(f"{name} has {a.size} entries, the obs has {OBS_DIM}")
-                self._arrays[name] = a
-                setattr(w, name, a.ctypes.data_as(_D))
-        self.activation = activation
-        self.clip_obs, self.epsilon = clip_obs, float(epsilon)
-        self.device_name = device
-        self._h = None          # ha_policy*, made with the first device call
-        self.device = None
-        self.h_pi = self.c_pi = self.h_vf = self.c_vf = None
-
-    def _set_tensors(self, weights):
-        if any("." in k for k in weights):
-            weights = policy_weights_from_state_dict(weights)
-        arrays = {}
-        for _, field, shape in POLICY_KEYS:
-            a = np.ascontiguousarray(weights[field], dtype=np.float32)
-            if a.shape != shape:
-                raise ValueError(f"{field} has shape {a.shape}, expected {shape}")
-            arrays[field] = a
-        self._arrays.update(arrays)   # the struct points into these: they live as long as it does
-        for field, a in arrays.items():
-            setattr(self._w, field, a.ctypes.data_as(_F))
-
-    # ------------------------------------------------------------------ loaders
-    @classmethod
-    def from_state_dict(cls, sd, normalization=None, **kw):
-        mean, var, over = _normalization(normalization)
-        return cls(policy_weights_from_state_dict(sd), obs_mean=mean, obs_var=var, **dict(over, **kw))
-
-    @classmethod
-    def from_sb3_zip(cls, path, normalization=None, **kw):
-        """An SB3 `model.save()` zip: its policy.pth is a plain torch state dict."""
-        import torch
-        with zipfile.ZipFile(path) as z:
-            sd = torch.load(io.BytesIO(z.read("policy.pth")), map_location="cpu", weights_only=True)
-        return cls.from_state_dict(sd, normalization=normalization, **kw)
+        super().__init__(weights, obs_mean, obs_var, clip_obs, epsilon, activation, device)
 
     def load_state_dict(self, sd):
         """New tensors (a state dict or {field: array}) after a PPO update: ha_policy_update re-packs
@@ -474,32 +465,7 @@ class RecurrentPolicy:
             import torch
             with torch.cuda.device(self.device):
                 st = self.lib.ha_policy_update(self._h, ctypes.byref(self._w))
-            self._check(self._h, st, "ha_policy_update")
-
-    def _check(self, handle, status, what):
-        if status != _lib.HE_OK:
-            msg = (self.lib.ha_policy_last_error(handle) or b"").decode()
-            if status in (_lib.HE_ESHAPE, _lib.HE_EINVAL):
-                raise ValueError(f"{what}: {msg}")
-            raise _lib.HedgeEnvError(f"{what} failed (status {status}): {msg}")
-
-    # ------------------------------------------------------------------ device
-    def _handle(self):
-        if self._h is None:
-            import torch
-            dev = torch.device(self.device_name)
-            if dev.type != "cuda" or not torch.cuda.is_available():
-                raise _lib.HedgeEnvError("RecurrentPolicy.step runs on a HIP device (cuda:N); host_step is the CPU build")
-            dev = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
-            h = ctypes.c_void_p()
-            with torch.cuda.device(dev):
-                self._check(None, self.lib.ha_policy_create(ctypes.byref(self._w), ctypes.byref(h)), "ha_policy_create")
-            self._h, self.device = h, dev
-        return self._h
-
-    def _stream(self):
-        from .vec_env import _raw_stream
-        return _raw_stream(self.device.index)
+            _check(self.lib, st, "ha_policy_update", self._h, "ha_policy_last_error")
 
     @property
     def states(self):
@@ -527,16 +493,9 @@ class RecurrentPolicy:
         step_index, env_id_offset + e) alone.  write_state=False leaves the LSTM states as they are
         (SB3's predict_values).  Enqueued on the current stream, no host sync."""
         import torch
-        h = self._handle()
-        n = int(obs.shape[0])
+        h, n, episode_start = self._begin_step(obs, episode_start)
         if self.h_pi is None or self.h_pi.shape[0] != n:
             self.reset_states(n)
-        if obs.dtype != torch.float32 or not obs.is_contiguous() or obs.device != self.device or obs.shape[1] != OBS_DIM:
-            raise ValueError(f"obs must be a contiguous float32 [n, {OBS_DIM}] tensor on {self.device}")
-        if episode_start.dtype == torch.bool:
-            episode_start = episode_start.view(torch.uint8)
-        if episode_start.dtype != torch.uint8 or episode_start.numel() != n or not episode_start.is_contiguous():
-            raise ValueError("episode_start must be a contiguous uint8 / bool [n] tensor")
         res = dict(out) if out else {}
         ptr = []
         for name, tail in STEP_OUTPUTS:
@@ -551,7 +510,7 @@ class RecurrentPolicy:
                                      int(bool(deterministic)), int(bool(write_state)), obs.data_ptr(),
                                      episode_start.data_ptr(), *(t.data_ptr() for t in self.states), *ptr,
                                      self._stream())
-        self._check(h, st, "ha_policy_step")
+        _check(self.lib, st, "ha_policy_step", h, "ha_policy_last_error")
         return res
 
     def gae(self, rewards, values, episode_starts, last_values, last_dones, gamma, gae_lambda, advantages=None,
@@ -578,7 +537,7 @@ class RecurrentPolicy:
         st = self.lib.ha_gae(n, K, float(gamma), float(gae_lambda), rewards.data_ptr(), values.data_ptr(),
                              u8[0].data_ptr(), last_values.data_ptr(), u8[1].data_ptr(), advantages.data_ptr(),
                              returns.data_ptr(), self._stream())
-        self._check(None, st, "ha_gae")
+        _check(self.lib, st, "ha_gae")
         return advantages, returns
 
     # ------------------------------------------------------------------ host
@@ -587,23 +546,15 @@ class RecurrentPolicy:
         """ha_host_policy_step over NumPy: obs [n,13], episode_start [n], states = (h_pi, c_pi, h_vf,
         c_vf), C-contiguous float32 [n,128] arrays updated IN PLACE (unless write_state=False) ->
         a dict of every output of STEP_OUTPUTS.  The device kernel's arithmetic on the CPU."""
-        obs = np.ascontiguousarray(obs, dtype=np.float32)
-        n = obs.shape[0]
-        es = np.ascontiguousarray(np.asarray(episode_start).reshape(-1), dtype=np.uint8)
-        if obs.shape != (n, OBS_DIM) or es.shape != (n,):
-            raise ValueError(f"obs must be [n, {OBS_DIM}] and episode_start [n]")
         if len(states) != 4:
             raise ValueError("states is (h_pi, c_pi, h_vf, c_vf)")
-        for name, a in zip(STATE_NAMES, states):
-            if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous
-                    and a.shape == (n, HIDDEN)):
-                raise ValueError(f"{name} must be a C-contiguous float32 [{n}, {HIDDEN}] array")
+        obs, es, n = self._host_inputs(obs, episode_start, STATE_NAMES, states)
         res = {name: np.empty((n,) + tail, np.float32) for name, tail in STEP_OUTPUTS}
         st = self.lib.ha_host_policy_step(ctypes.byref(self._w), n, int(env_id_offset), int(seed) & (2 ** 64 - 1),
                                           int(step_index), int(bool(deterministic)), int(bool(write_state)),
                                           obs.ctypes.data, es.ctypes.data, *(a.ctypes.data for a in states),
                                           *(res[name].ctypes.data for name, _ in STEP_OUTPUTS))
-        self._check(None, st, "ha_host_policy_step")
+        _check(self.lib, st, "ha_host_policy_step")
         return res
 
     def host_gae(self, rewards, values, episode_starts, last_values, last_dones, gamma, gae_lambda):
@@ -620,19 +571,5 @@ class RecurrentPolicy:
         ret = np.empty((K, n), np.float32)
         st = self.lib.ha_host_gae(n, K, float(gamma), float(gae_lambda), rewards.ctypes.data, values.ctypes.data,
                                   es.ctypes.data, lv.ctypes.data, ld.ctypes.data, adv.ctypes.data, ret.ctypes.data)
-        self._check(None, st, "ha_host_gae")
+        _check(self.lib, st, "ha_host_gae")
         return adv, ret
-
-    def close(self):
-        if self._h is not None:
-            import torch
-            torch.cuda.synchronize(self.device)
-            self.lib.ha_policy_destroy(self._h)
-            self._h = None
-        self.h_pi = self.c_pi = self.h_vf = self.c_vf = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

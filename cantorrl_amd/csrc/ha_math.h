@@ -42,19 +42,8 @@ HE_HD float norm_obs(float o, double mean, double sd, double y, bool has_clip, d
     return (float)q;
 }
 
-// the LSTM cell from the four pre-activations: c' into *c, returns h'
-HE_HD float cell_update(float pi, float pf, float pg, float po, float* c) {
-    const float i = sigmoidf_r(pi), f = sigmoidf_r(pf), o = sigmoidf_r(po);
-    const float g = tanhf_r(pg);
-    const float fc = f * *c;
-    const float ig = i * g;
-    const float cn = fc + ig;
-    *c = cn;
-    return o * tanhf_r(cn);
-}
-
-// cell_update that also hands out the four activations (contract F2): the same operations in the
-// same order, so c' and h' are cell_update's bits
+// the LSTM cell from the four pre-activations: c' into *c, the four activations into gate[i, f, g, o]
+// (contract F2), returns h'
 HE_HD float cell_forward(float pi, float pf, float pg, float po, float* c, float* gate) {
     const float i = sigmoidf_r(pi), f = sigmoidf_r(pf), o = sigmoidf_r(po);
     const float g = tanhf_r(pg);
@@ -64,6 +53,12 @@ HE_HD float cell_forward(float pi, float pf, float pg, float po, float* c, float
     *c = cn;
     gate[0] = i, gate[1] = f, gate[2] = g, gate[3] = o;
     return o * tanhf_r(cn);
+}
+
+// cell_forward without the activations
+HE_HD float cell_update(float pi, float pf, float pg, float po, float* c) {
+    float gate[4];
+    return cell_forward(pi, pf, pg, po, c, gate);
 }
 
 // Contract B2-B3 for one (unit, env) at one step: the gradient of the four pre-activations into

@@ -155,7 +155,7 @@ __device__ __forceinline__ void net_tile(Tile& t, const Net& net, int64_t n, int
     if (tid < kTile) t.xh[kKx][tid] = 0.0f;
     __syncthreads();
 
-    // ---- gates: wave = unit group, four accumulators
+    // ---- gates: wave = unit group, four accumulators (lstm_seq_fwd_kernel's copy of this product: see there)
     const int wave = tid >> 6, lane = tid & 63;
     const int col = lane & 31, hi = lane >> 5;
     {
@@ -338,8 +338,45 @@ ha_status fail_to(char* err, ha_status st, const char* msg) {
     snprintf(err ? err : g_err, 256, "%s", msg);
     return st;
 }
-ha_status fail(ha_actor* a, ha_status st, const char* msg) { return fail_to(a ? a->err : nullptr, st, msg); }
-ha_status fail(ha_policy* a, ha_status st, const char* msg) { return fail_to(a ? a->err : nullptr, st, msg); }
+template <class H>   // ha_actor or ha_policy; NULL: the thread's message
+ha_status fail(H* a, ha_status st, const char* msg) { return fail_to(a ? a->err : nullptr, st, msg); }
+
+// one kernel launch on `stream`: HE_OK, or HE_EHIP with "<name> launch failed" in err (NULL: the thread's)
+template <class K, class... A>
+ha_status launch(char* err, K kernel, dim3 grid, dim3 block, void* stream, const char* name, const A&... args) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, args...);
+    if (hipGetLastError() == hipSuccess) return HE_OK;
+    char m[96];
+    snprintf(m, sizeof m, "%s launch failed", name);
+    return fail_to(err, HE_EHIP, m);
+}
+
+// The packed tensors to the device: into *blob, allocated first where it is NULL (and freed again
+// when the copy fails: the caller drops its handle).  Messages go to err (NULL: the thread's).
+ha_status upload_blob(const std::vector<float>& hbuf, void** blob, char* err) {
+    const size_t bytes = hbuf.size() * sizeof(float);
+    const bool fresh = !*blob;
+    if (fresh && hipMalloc(blob, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail_to(err, HE_ENOMEM, "hipMalloc of the packed weights failed (no HIP device?)");
+    }
+    if (hipMemcpy(*blob, hbuf.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        if (fresh) (void)hipFree(*blob);
+        return fail_to(err, HE_EHIP, "upload of the packed weights failed");
+    }
+    return HE_OK;
+}
+
+// a new ha_actor / ha_policy around the uploaded blob; its p is the caller's to fill
+template <class H>
+ha_status create_handle(const std::vector<float>& hbuf, H** out) {
+    H* a = new (std::nothrow) H();   // value-initialised: no message, no blob
+    if (!a) return fail_to(nullptr, HE_ENOMEM, "host allocation failed");
+    const ha_status st = upload_blob(hbuf, &a->blob, nullptr);
+    if (st != HE_OK) delete a;
+    else *out = a;
+    return st;
+}
 
 // one network's HOST tensors, torch layout; w3 is [n_out][64]
 struct HostNet {
@@ -348,57 +385,55 @@ struct HostNet {
     bool complete() const { return w_ih && w_hh && b_ih && b_hh && w1 && b1 && w2 && b2 && w3 && b3; }
 };
 
-HostNet actor_net(const ha_weights* w) {
-    return {w->w_ih, w->w_hh, w->b_ih, w->b_hh, w->w1, w->b1, w->w2, w->b2, w->w3, w->b3, kAct};
-}
-HostNet actor_net(const ha_policy_weights* w) {
+template <class W>   // ha_weights or ha_policy_weights
+HostNet actor_net(const W* w) {
     return {w->w_ih, w->w_hh, w->b_ih, w->b_hh, w->w1, w->b1, w->w2, w->b2, w->w3, w->b3, kAct};
 }
 HostNet critic_net(const ha_policy_weights* w) {
     return {w->c_w_ih, w->c_w_hh, w->c_b_ih, w->c_b_hh, w->v1, w->vb1, w->v2, w->vb2, w->v3, w->vb3, 1};
 }
 
+// The header fields ha_weights and ha_policy_weights share: n_lstm_layers, the four dimensions,
+// activation and the mean / var pairing.  layers, what, built: the words their messages differ in;
+// rest: the caller's own finding (squash, a NULL tensor) or NULL, reported where it always stood,
+// after the activation.
+template <class W>
+ha_status check_header(const W* w, char* err, const char* layers, const char* what, const char* built,
+                       const char* rest) {
+    char m[200];
+    if (w->n_lstm_layers != 1) {
+        snprintf(m, sizeof m, "n_lstm_layers = %d: %s", w->n_lstm_layers, layers);
+        return fail_to(err, HE_ESHAPE, m);
+    }
+    if (w->obs_dim != kObs || w->hidden != kHid || w->mlp_width != kMlp || w->act_dim != kAct) {
+        snprintf(m, sizeof m, "%s shape obs %d / lstm %d / mlp %d / action %d: only %s is built", what, w->obs_dim,
+                 w->hidden, w->mlp_width, w->act_dim, built);
+        return fail_to(err, HE_ESHAPE, m);
+    }
+    if (w->activation != HA_ACT_TANH && w->activation != HA_ACT_RELU) return fail_to(err, HE_EINVAL, "unknown activation");
+    if (rest) return fail_to(err, HE_EINVAL, rest);
+    if ((w->obs_mean == nullptr) != (w->obs_var == nullptr))
+        return fail_to(err, HE_EINVAL, "obs_mean and obs_var come together");
+    return HE_OK;
+}
+
 ha_status check_weights(const ha_weights* w, ha_actor* a) {
     if (!w) return fail(a, HE_EINVAL, "weights is NULL");
     if (w->abi_version != HA_ABI_VERSION) return fail(a, HE_EINVAL, "ha_weights.abi_version mismatch");
-    char m[200];
-    if (w->n_lstm_layers != 1) {
-        snprintf(m, sizeof m, "n_lstm_layers = %d: this actor has one LSTM layer", w->n_lstm_layers);
-        return fail(a, HE_ESHAPE, m);
-    }
-    if (w->obs_dim != kObs || w->hidden != kHid || w->mlp_width != kMlp || w->act_dim != kAct) {
-        snprintf(m, sizeof m, "actor shape obs %d / lstm %d / mlp %d / action %d: only 13 / 128 / 64 / 2 is built",
-                 w->obs_dim, w->hidden, w->mlp_width, w->act_dim);
-        return fail(a, HE_ESHAPE, m);
-    }
-    if (w->activation != HA_ACT_TANH && w->activation != HA_ACT_RELU) return fail(a, HE_EINVAL, "unknown activation");
-    if (w->squash != HA_SQUASH_CLIP && w->squash != HA_SQUASH_TANH) return fail(a, HE_EINVAL, "unknown squash");
-    if (!actor_net(w).complete()) return fail(a, HE_EINVAL, "an actor tensor is NULL");
-    if ((w->obs_mean == nullptr) != (w->obs_var == nullptr))
-        return fail(a, HE_EINVAL, "obs_mean and obs_var come together");
-    return HE_OK;
+    const char* rest = w->squash != HA_SQUASH_CLIP && w->squash != HA_SQUASH_TANH ? "unknown squash"
+                       : !actor_net(w).complete()                                 ? "an actor tensor is NULL"
+                                                                                  : nullptr;
+    return check_header(w, a ? a->err : nullptr, "this actor has one LSTM layer", "actor", "13 / 128 / 64 / 2", rest);
 }
 
 ha_status check_policy_weights(const ha_policy_weights* w, ha_policy* a) {
     if (!w) return fail(a, HE_EINVAL, "weights is NULL");
     if (w->abi_version != HA_POLICY_ABI_VERSION) return fail(a, HE_EINVAL, "ha_policy_weights.abi_version mismatch");
-    char m[200];
-    if (w->n_lstm_layers != 1) {
-        snprintf(m, sizeof m, "n_lstm_layers = %d: actor and critic have one LSTM layer each", w->n_lstm_layers);
-        return fail(a, HE_ESHAPE, m);
-    }
-    if (w->obs_dim != kObs || w->hidden != kHid || w->mlp_width != kMlp || w->act_dim != kAct) {
-        snprintf(m, sizeof m,
-                 "policy shape obs %d / lstm %d / mlp %d / action %d: only 13 / 128 / 64-64 / 2 actions / 1 value is built",
-                 w->obs_dim, w->hidden, w->mlp_width, w->act_dim);
-        return fail(a, HE_ESHAPE, m);
-    }
-    if (w->activation != HA_ACT_TANH && w->activation != HA_ACT_RELU) return fail(a, HE_EINVAL, "unknown activation");
-    if (!actor_net(w).complete() || !w->log_std) return fail(a, HE_EINVAL, "an actor tensor (or log_std) is NULL");
-    if (!critic_net(w).complete()) return fail(a, HE_EINVAL, "a critic tensor is NULL");
-    if ((w->obs_mean == nullptr) != (w->obs_var == nullptr))
-        return fail(a, HE_EINVAL, "obs_mean and obs_var come together");
-    return HE_OK;
+    const char* rest = !actor_net(w).complete() || !w->log_std ? "an actor tensor (or log_std) is NULL"
+                       : !critic_net(w).complete()             ? "a critic tensor is NULL"
+                                                               : nullptr;
+    return check_header(w, a ? a->err : nullptr, "actor and critic have one LSTM layer each", "policy",
+                        "13 / 128 / 64-64 / 2 actions / 1 value", rest);
 }
 
 // W[j][k] of the gate product over [x | h | 0]
@@ -436,16 +471,7 @@ void pack_net(const HostNet& w, float* dst) {
 }
 
 Net net_at(const float* d) {
-    Net n;
-    n.wg = (const float4*)(d + o_wg);
-    n.bg = d + o_bg;
-    n.w1p = d + o_w1;
-    n.b1 = d + o_b1;
-    n.w2p = d + o_w2;
-    n.b2 = d + o_b2;
-    n.w3 = d + o_w3;
-    n.b3 = d + o_b3;
-    return n;
+    return {(const float4*)(d + o_wg), d + o_bg, d + o_w1, d + o_b1, d + o_w2, d + o_b2, d + o_w3, d + o_b3};
 }
 
 // [3][13] mean, sd = sqrt(var + eps), RN(1 / sd) at an 8-byte aligned dst
@@ -459,22 +485,55 @@ void pack_stats(const double* mean, const double* var, double epsilon, float* ds
     memcpy(dst, stt, sizeof stt);
 }
 
+// the host's gate operand [x | h, zeroed when fresh | 0]
+void host_xh(const float* x, const float* h, bool fresh, float* xh) {
+    for (int k = 0; k < kObs; ++k) xh[k] = x[k];
+    for (int u = 0; u < kHid; ++u) xh[kObs + u] = fresh ? 0.0f : h[u];
+    xh[kKx] = 0.0f;
+}
+
+// THE gate chain of the contract on the host: the four pre-activations of unit u, each from
+// b_ih + b_hh through fmaf over k = 0 .. kKp - 1 of xh
+void host_gates(const HostNet& w, const float* xh, int u, float* pre) {
+    for (int g = 0; g < 4; ++g) {
+        const int j = g * kHid + u;
+        float acc = w.b_ih[j] + w.b_hh[j];
+        for (int k = 0; k < kKp; ++k) acc = fmaf(gate_w(w, j, k), xh[k], acc);
+        pre[g] = acc;
+    }
+}
+
+// Contract step 2 on the host: sd = sqrt(var + eps) and y = RN(1 / sd) once, then env(): env e's obs
+// into x[kObs], and into obs_norm_out's row e where that is given
+struct HostNorm {
+    const double* mean;   // NULL: the obs are used as they come
+    double sd[kObs], y[kObs], clip;
+    bool has_clip;
+    HostNorm(const double* obs_mean, const double* obs_var, double epsilon, bool has_clip_, double clip_obs)
+        : mean(obs_mean), clip(clip_obs), has_clip(has_clip_) {
+        for (int k = 0; mean && k < kObs; ++k) {
+            sd[k] = sqrt(obs_var[k] + epsilon);
+            y[k] = 1.0 / sd[k];
+        }
+    }
+    void env(const float* obs, int64_t e, float* x, float* obs_norm_out) const {
+        for (int k = 0; k < kObs; ++k) {
+            float v = obs[e * kObs + k];
+            if (mean) v = norm_obs(v, mean[k], sd[k], y[k], has_clip, clip);
+            if (obs_norm_out) obs_norm_out[e * kObs + k] = v;
+            x[k] = v;
+        }
+    }
+};
+
 // Contract steps 1, 3-5 for one env on the host: x is the (normalised) obs; h, c are read unless
 // fresh and written when write_state; a2 receives the last hidden layer.
 void host_net_env(const HostNet& w, const float* x, bool fresh, float* h, float* c, bool write_state, bool relu,
                   float* a2) {
-    float xh[kKp], hn[kHid], cn[kHid], a1[kMlp];
-    for (int k = 0; k < kObs; ++k) xh[k] = x[k];
-    for (int u = 0; u < kHid; ++u) xh[kObs + u] = fresh ? 0.0f : h[u];
-    xh[kKx] = 0.0f;
+    float xh[kKp], hn[kHid], cn[kHid], a1[kMlp], pre[4];
+    host_xh(x, h, fresh, xh);
     for (int u = 0; u < kHid; ++u) {
-        float pre[4];
-        for (int g = 0; g < 4; ++g) {
-            const int j = g * kHid + u;
-            float acc = w.b_ih[j] + w.b_hh[j];
-            for (int k = 0; k < kKp; ++k) acc = fmaf(gate_w(w, j, k), xh[k], acc);
-            pre[g] = acc;
-        }
+        host_gates(w, xh, u, pre);
         float cv = fresh ? 0.0f : c[u];
         hn[u] = cell_update(pre[0], pre[1], pre[2], pre[3], &cv);
         cn[u] = cv;
@@ -674,7 +733,7 @@ __global__ __launch_bounds__(kThreads, 2) void lstm_seq_fwd_kernel(const SeqFwdP
         const float* bgs = bg;
         const float4* wps = wp;
         asm volatile("" : "+s"(bgs), "+v"(wps));
-        f32x16 acc[4];
+        f32x16 acc[4];   // net_tile's gate product: a shared inline moves both code objects, so there are two copies
 #pragma unroll
         for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -812,7 +871,14 @@ ha_status check_seq(int64_t n_nets, int64_t L, int64_t B) {
 
 inline bool bad_ptr(const void* q, uintptr_t mask) { return !q || (((uintptr_t)q) & mask); }
 
-ha_status check_seq_fwd(int64_t n_nets, const void* x, const void* starts, const ha_lstm_seq_net* nets, uintptr_t mask) {
+ha_status check_workspace(const void* workspace) {
+    return bad_ptr(workspace, 15u) ? fail_to(nullptr, HE_EINVAL, "workspace must be non-NULL and 16-byte aligned") : HE_OK;
+}
+
+ha_status check_seq_fwd(int64_t n_nets, int64_t L, int64_t B, const void* x, const void* starts,
+                        const ha_lstm_seq_net* nets, uintptr_t mask) {
+    const ha_status st = check_seq(n_nets, L, B);
+    if (st != HE_OK) return st;
     if (!nets) return fail_to(nullptr, HE_EINVAL, "nets is NULL");
     if (bad_ptr(x, mask) || bad_ptr(starts, mask))
         return fail_to(nullptr, HE_EINVAL, "x and episode_starts must be non-NULL and 16-byte aligned");
@@ -826,7 +892,10 @@ ha_status check_seq_fwd(int64_t n_nets, const void* x, const void* starts, const
     return HE_OK;
 }
 
-ha_status check_seq_bwd(int64_t n_nets, const void* starts, const ha_lstm_seq_bwd* nets, uintptr_t mask) {
+ha_status check_seq_bwd(int64_t n_nets, int64_t L, int64_t B, const void* starts, const ha_lstm_seq_bwd* nets,
+                        uintptr_t mask) {
+    const ha_status st = check_seq(n_nets, L, B);
+    if (st != HE_OK) return st;
     if (!nets) return fail_to(nullptr, HE_EINVAL, "nets is NULL");
     if (bad_ptr(starts, mask)) return fail_to(nullptr, HE_EINVAL, "episode_starts must be non-NULL and 16-byte aligned");
     for (int64_t k = 0; k < n_nets; ++k) {
@@ -1120,7 +1189,7 @@ const char* ha_last_error(const ha_actor* actor) { return actor ? actor->err : g
 const char* ha_policy_last_error(const ha_policy* policy) { return policy ? policy->err : g_err; }
 
 ha_status ha_create(const ha_weights* w, ha_actor** out) {
-    if (!out) return fail((ha_actor*)nullptr, HE_EINVAL, "out is NULL");
+    if (!out) return fail_to(nullptr, HE_EINVAL, "out is NULL");
     *out = nullptr;
     ha_status st = check_weights(w, nullptr);
     if (st != HE_OK) return st;
@@ -1129,22 +1198,10 @@ ha_status ha_create(const ha_weights* w, ha_actor** out) {
     std::vector<float> hbuf(total, 0.0f);
     pack_net(actor_net(w), hbuf.data());
     if (w->obs_mean) pack_stats(w->obs_mean, w->obs_var, w->epsilon, &hbuf[o_st]);
-    ha_actor* a = new (std::nothrow) ha_actor();
-    if (!a) return fail((ha_actor*)nullptr, HE_ENOMEM, "host allocation failed");
-    a->err[0] = 0;
-    a->blob = nullptr;
-    if (hipMalloc(&a->blob, total * sizeof(float)) != hipSuccess) {
-        delete a;
-        (void)hipGetLastError();
-        return fail((ha_actor*)nullptr, HE_ENOMEM, "hipMalloc of the packed weights failed (no HIP device?)");
-    }
-    if (hipMemcpy(a->blob, hbuf.data(), total * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(a->blob);
-        delete a;
-        return fail((ha_actor*)nullptr, HE_EHIP, "upload of the packed weights failed");
-    }
-    const float* d = (const float*)a->blob;
-    Params& p = a->p;
+    st = create_handle(hbuf, out);
+    if (st != HE_OK) return st;
+    const float* d = (const float*)(*out)->blob;
+    Params& p = (*out)->p;
     memset(&p, 0, sizeof p);
     p.net = net_at(d);
     p.stats = w->obs_mean ? (const double*)(d + o_st) : nullptr;
@@ -1152,7 +1209,6 @@ ha_status ha_create(const ha_weights* w, ha_actor** out) {
     p.has_clip = w->has_clip;
     p.relu = w->activation == HA_ACT_RELU;
     p.tanh_squash = w->squash == HA_SQUASH_TANH;
-    *out = a;
     return HE_OK;
 }
 
@@ -1179,9 +1235,7 @@ ha_status ha_step(ha_actor* actor, int64_t n, const float* obs, const uint8_t* e
     p.mean_out = mean_out;
     p.obs_norm_out = obs_norm_out;
     const unsigned grid = (unsigned)((n + kTile - 1) / kTile);
-    hipLaunchKernelGGL(actor_kernel, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, p);
-    if (hipGetLastError() != hipSuccess) return fail(actor, HE_EHIP, "actor_kernel launch failed");
-    return HE_OK;
+    return launch(actor->err, actor_kernel, dim3(grid), dim3(kThreads), stream, "actor_kernel", p);
 }
 
 ha_status ha_accumulate(ha_actor* actor, int64_t n, int64_t env_id_offset, const double* reward_step,
@@ -1199,10 +1253,8 @@ ha_status ha_accumulate(ha_actor* actor, int64_t n, int64_t env_id_offset, const
     if (!terminated || !sums || !count) return fail(actor, HE_EINVAL, "terminated, sums and count are required");
     if (capacity < 0 || (capacity > 0 && !records)) return fail(actor, HE_EINVAL, "records is NULL with capacity > 0");
     const unsigned grid = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(accumulate_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, n, env_id_offset, in, terminated,
-                       sums, records, capacity, count);
-    if (hipGetLastError() != hipSuccess) return fail(actor, HE_EHIP, "accumulate_kernel launch failed");
-    return HE_OK;
+    return launch(actor->err, accumulate_kernel, dim3(grid), dim3(256), stream, "accumulate_kernel", n, env_id_offset, in,
+                  terminated, sums, records, capacity, count);
 }
 
 ha_status ha_host_step(const ha_weights* w, int64_t n, const float* obs, const uint8_t* episode_start, float* h,
@@ -1210,23 +1262,13 @@ ha_status ha_host_step(const ha_weights* w, int64_t n, const float* obs, const u
     ha_status st = check_weights(w, nullptr);
     if (st != HE_OK) return st;
     if (n < 1 || !obs || !episode_start || !h || !c || !actions)
-        return fail((ha_actor*)nullptr, HE_EINVAL, "bad argument");
-    double sd[kObs], y[kObs];
-    if (w->obs_mean)
-        for (int k = 0; k < kObs; ++k) {
-            sd[k] = sqrt(w->obs_var[k] + w->epsilon);
-            y[k] = 1.0 / sd[k];
-        }
+        return fail_to(nullptr, HE_EINVAL, "bad argument");
+    const HostNorm norm(w->obs_mean, w->obs_var, w->epsilon, w->has_clip != 0, w->clip_obs);
     const bool relu = w->activation == HA_ACT_RELU, tsq = w->squash == HA_SQUASH_TANH;
     const HostNet net = actor_net(w);
     for (int64_t e = 0; e < n; ++e) {
         float x[kObs], a2[kMlp];
-        for (int k = 0; k < kObs; ++k) {
-            float v = obs[e * kObs + k];
-            if (w->obs_mean) v = norm_obs(v, w->obs_mean[k], sd[k], y[k], w->has_clip != 0, w->clip_obs);
-            if (obs_norm_out) obs_norm_out[e * kObs + k] = v;
-            x[k] = v;
-        }
+        norm.env(obs, e, x, obs_norm_out);
         host_net_env(net, x, episode_start[e] != 0, h + e * kHid, c + e * kHid, true, relu, a2);
         for (int j = 0; j < kAct; ++j) {
             const float m = host_head(net, j, a2);
@@ -1238,29 +1280,15 @@ ha_status ha_host_step(const ha_weights* w, int64_t n, const float* obs, const u
 }
 
 ha_status ha_policy_create(const ha_policy_weights* w, ha_policy** out) {
-    if (!out) return fail((ha_policy*)nullptr, HE_EINVAL, "out is NULL");
+    if (!out) return fail_to(nullptr, HE_EINVAL, "out is NULL");
     *out = nullptr;
     ha_status st = check_policy_weights(w, nullptr);
     if (st != HE_OK) return st;
     std::vector<float> hbuf(kPolicyFloats, 0.0f);
     pack_policy(w, hbuf.data());
-    ha_policy* a = new (std::nothrow) ha_policy();
-    if (!a) return fail((ha_policy*)nullptr, HE_ENOMEM, "host allocation failed");
-    a->err[0] = 0;
-    a->blob = nullptr;
-    if (hipMalloc(&a->blob, kPolicyFloats * sizeof(float)) != hipSuccess) {
-        delete a;
-        (void)hipGetLastError();
-        return fail((ha_policy*)nullptr, HE_ENOMEM, "hipMalloc of the packed weights failed (no HIP device?)");
-    }
-    if (hipMemcpy(a->blob, hbuf.data(), kPolicyFloats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(a->blob);
-        delete a;
-        return fail((ha_policy*)nullptr, HE_EHIP, "upload of the packed weights failed");
-    }
-    policy_params(w, (const float*)a->blob, &a->p);
-    *out = a;
-    return HE_OK;
+    st = create_handle(hbuf, out);
+    if (st == HE_OK) policy_params(w, (const float*)(*out)->blob, &(*out)->p);
+    return st;
 }
 
 ha_status ha_policy_destroy(ha_policy* policy) {
@@ -1278,10 +1306,9 @@ ha_status ha_policy_update(ha_policy* policy, const ha_policy_weights* w) {
     pack_policy(w, hbuf.data());
     // steps already enqueued read the old tensors to their end
     if (hipDeviceSynchronize() != hipSuccess) return fail(policy, HE_EHIP, "hipDeviceSynchronize failed");
-    if (hipMemcpy(policy->blob, hbuf.data(), kPolicyFloats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(policy, HE_EHIP, "upload of the packed weights failed");
-    policy_params(w, (const float*)policy->blob, &policy->p);
-    return HE_OK;
+    st = upload_blob(hbuf, &policy->blob, policy->err);
+    if (st == HE_OK) policy_params(w, (const float*)policy->blob, &policy->p);
+    return st;
 }
 
 ha_status ha_policy_step(ha_policy* policy, int64_t n, int64_t env_id_offset, uint64_t seed, uint64_t step_index,
@@ -1317,9 +1344,7 @@ ha_status ha_policy_step(ha_policy* policy, int64_t n, int64_t env_id_offset, ui
     p.mean_out = mean_out;
     p.obs_norm_out = obs_norm_out;
     const unsigned grid = (unsigned)((n + kTile - 1) / kTile);
-    hipLaunchKernelGGL(policy_step_kernel, dim3(grid, 2), dim3(kThreads), 0, (hipStream_t)stream, p);
-    if (hipGetLastError() != hipSuccess) return fail(policy, HE_EHIP, "policy_step_kernel launch failed");
-    return HE_OK;
+    return launch(policy->err, policy_step_kernel, dim3(grid, 2), dim3(kThreads), stream, "policy_step_kernel", p);
 }
 
 ha_status ha_gae(int64_t n, int64_t K, double gamma, double gae_lambda, const float* rewards, const float* values,
@@ -1330,11 +1355,9 @@ ha_status ha_gae(int64_t n, int64_t K, double gamma, double gae_lambda, const fl
     if (st != HE_OK) return st;
     if (n > ((int64_t)1 << 30)) return fail_to(nullptr, HE_EINVAL, "n must be <= 2^30");
     const unsigned grid = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(gae_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, n, K, (float)gamma,
-                       (float)(gamma * gae_lambda), rewards, values, episode_starts, last_values, last_dones, advantages,
-                       returns);
-    if (hipGetLastError() != hipSuccess) return fail_to(nullptr, HE_EHIP, "gae_kernel launch failed");
-    return HE_OK;
+    return launch(nullptr, gae_kernel, dim3(grid), dim3(256), stream, "gae_kernel", n, K, (float)gamma,
+                  (float)(gamma * gae_lambda), rewards, values, episode_starts, last_values, last_dones, advantages,
+                  returns);
 }
 
 ha_status ha_host_policy_step(const ha_policy_weights* w, int64_t n, int64_t env_id_offset, uint64_t seed,
@@ -1346,24 +1369,14 @@ ha_status ha_host_policy_step(const ha_policy_weights* w, int64_t n, int64_t env
     if (st != HE_OK) return st;
     if (n < 1 || env_id_offset < 0 || !obs || !episode_start || !h_pi || !c_pi || !h_vf || !c_vf || !actions ||
         !env_actions || !values || !log_probs)
-        return fail((ha_policy*)nullptr, HE_EINVAL, "bad argument");
-    double sd[kObs], y[kObs];
-    if (w->obs_mean)
-        for (int k = 0; k < kObs; ++k) {
-            sd[k] = sqrt(w->obs_var[k] + w->epsilon);
-            y[k] = 1.0 / sd[k];
-        }
+        return fail_to(nullptr, HE_EINVAL, "bad argument");
+    const HostNorm norm(w->obs_mean, w->obs_var, w->epsilon, w->has_clip != 0, w->clip_obs);
     const bool relu = w->activation == HA_ACT_RELU;
     const HostNet pi = actor_net(w), vf = critic_net(w);
     const float stdv[kAct] = {policy_std(w->log_std[0]), policy_std(w->log_std[1])};
     for (int64_t e = 0; e < n; ++e) {
         float x[kObs], a2[kMlp], mean[kAct];
-        for (int k = 0; k < kObs; ++k) {
-            float v = obs[e * kObs + k];
-            if (w->obs_mean) v = norm_obs(v, w->obs_mean[k], sd[k], y[k], w->has_clip != 0, w->clip_obs);
-            if (obs_norm_out) obs_norm_out[e * kObs + k] = v;
-            x[k] = v;
-        }
+        norm.env(obs, e, x, obs_norm_out);
         const bool fresh = episode_start[e] != 0;
         host_net_env(pi, x, fresh, h_pi + e * kHid, c_pi + e * kHid, write_state != 0, relu, a2);
         for (int j = 0; j < kAct; ++j) {
@@ -1396,15 +1409,11 @@ size_t ha_lstm_seq_workspace_bytes(int64_t n_nets) {
 
 ha_status ha_lstm_seq_forward(int64_t n_nets, int64_t L, int64_t B, const float* x, const uint8_t* episode_starts,
                               const ha_lstm_seq_net* nets, void* workspace, void* stream) {
-    ha_status st = check_seq(n_nets, L, B);
+    ha_status st = check_seq_fwd(n_nets, L, B, x, episode_starts, nets, 15u);
+    if (st == HE_OK) st = check_workspace(workspace);
     if (st != HE_OK) return st;
-    st = check_seq_fwd(n_nets, x, episode_starts, nets, 15u);
-    if (st != HE_OK) return st;
-    if (bad_ptr(workspace, 15u)) return fail_to(nullptr, HE_EINVAL, "workspace must be non-NULL and 16-byte aligned");
-    SeqPackParams pk;
-    SeqFwdParams p;
-    memset(&pk, 0, sizeof pk);
-    memset(&p, 0, sizeof p);
+    SeqPackParams pk = {};
+    SeqFwdParams p = {};
     for (int64_t k = 0; k < n_nets; ++k) {
         pk.w_ih[k] = nets[k].w_ih;
         pk.w_hh[k] = nets[k].w_hh;
@@ -1418,25 +1427,21 @@ ha_status ha_lstm_seq_forward(int64_t n_nets, int64_t L, int64_t B, const float*
     p.x = x;
     p.start = episode_starts;
     p.ws = (const float*)workspace;
-    hipLaunchKernelGGL(lstm_seq_pack_fwd_kernel, dim3(72, (unsigned)n_nets), dim3(256), 0, (hipStream_t)stream, pk);
-    if (hipGetLastError() != hipSuccess) return fail_to(nullptr, HE_EHIP, "lstm_seq_pack_fwd_kernel launch failed");
+    st = launch(nullptr, lstm_seq_pack_fwd_kernel, dim3(72, (unsigned)n_nets), dim3(256), stream,
+                "lstm_seq_pack_fwd_kernel", pk);
+    if (st != HE_OK) return st;
     const unsigned grid = (unsigned)((B + kTile - 1) / kTile);
-    hipLaunchKernelGGL(lstm_seq_fwd_kernel, dim3(grid, (unsigned)n_nets), dim3(kThreads), 0, (hipStream_t)stream, p);
-    if (hipGetLastError() != hipSuccess) return fail_to(nullptr, HE_EHIP, "lstm_seq_fwd_kernel launch failed");
-    return HE_OK;
+    return launch(nullptr, lstm_seq_fwd_kernel, dim3(grid, (unsigned)n_nets), dim3(kThreads), stream,
+                  "lstm_seq_fwd_kernel", p);
 }
 
 ha_status ha_lstm_seq_backward(int64_t n_nets, int64_t L, int64_t B, const uint8_t* episode_starts,
                                const ha_lstm_seq_bwd* nets, void* workspace, void* stream) {
-    ha_status st = check_seq(n_nets, L, B);
+    ha_status st = check_seq_bwd(n_nets, L, B, episode_starts, nets, 15u);
+    if (st == HE_OK) st = check_workspace(workspace);
     if (st != HE_OK) return st;
-    st = check_seq_bwd(n_nets, episode_starts, nets, 15u);
-    if (st != HE_OK) return st;
-    if (bad_ptr(workspace, 15u)) return fail_to(nullptr, HE_EINVAL, "workspace must be non-NULL and 16-byte aligned");
-    SeqPackParams pk;
-    SeqBwdParams p;
-    memset(&pk, 0, sizeof pk);
-    memset(&p, 0, sizeof p);
+    SeqPackParams pk = {};
+    SeqBwdParams p = {};
     for (int64_t k = 0; k < n_nets; ++k) {
         pk.w_hh[k] = nets[k].w_hh;
         p.net[k] = nets[k];
@@ -1446,19 +1451,17 @@ ha_status ha_lstm_seq_backward(int64_t n_nets, int64_t L, int64_t B, const uint8
     p.B = B;
     p.start = episode_starts;
     p.ws = (const float*)workspace;
-    hipLaunchKernelGGL(lstm_seq_pack_bwd_kernel, dim3(64, (unsigned)n_nets), dim3(256), 0, (hipStream_t)stream, pk);
-    if (hipGetLastError() != hipSuccess) return fail_to(nullptr, HE_EHIP, "lstm_seq_pack_bwd_kernel launch failed");
+    st = launch(nullptr, lstm_seq_pack_bwd_kernel, dim3(64, (unsigned)n_nets), dim3(256), stream,
+                "lstm_seq_pack_bwd_kernel", pk);
+    if (st != HE_OK) return st;
     const unsigned grid = (unsigned)((B + kTile - 1) / kTile);
-    hipLaunchKernelGGL(lstm_seq_bwd_kernel, dim3(grid, (unsigned)n_nets), dim3(kThreads), 0, (hipStream_t)stream, p);
-    if (hipGetLastError() != hipSuccess) return fail_to(nullptr, HE_EHIP, "lstm_seq_bwd_kernel launch failed");
-    return HE_OK;
+    return launch(nullptr, lstm_seq_bwd_kernel, dim3(grid, (unsigned)n_nets), dim3(kThreads), stream,
+                  "lstm_seq_bwd_kernel", p);
 }
 
 ha_status ha_host_lstm_seq_forward(int64_t n_nets, int64_t L, int64_t B, const float* x,
                                    const uint8_t* episode_starts, const ha_lstm_seq_net* nets) {
-    ha_status st = check_seq(n_nets, L, B);
-    if (st != HE_OK) return st;
-    st = check_seq_fwd(n_nets, x, episode_starts, nets, 0u);
+    const ha_status st = check_seq_fwd(n_nets, L, B, x, episode_starts, nets, 0u);
     if (st != HE_OK) return st;
     for (int64_t k = 0; k < n_nets; ++k) {
         const ha_lstm_seq_net& n = nets[k];
@@ -1470,17 +1473,10 @@ ha_status ha_host_lstm_seq_forward(int64_t n_nets, int64_t L, int64_t B, const f
             for (int64_t t = 0; t < L; ++t) {
                 const int64_t row = t * B + e;
                 const bool fresh = episode_starts[row] != 0;
-                for (int i = 0; i < kObs; ++i) xh[i] = x[row * kObs + i];
-                for (int u = 0; u < kHid; ++u) xh[kObs + u] = fresh ? 0.0f : h[u];
-                xh[kKx] = 0.0f;
+                host_xh(x + row * kObs, h, fresh, xh);
                 for (int u = 0; u < kHid; ++u) {
                     float pre[4], gt[4];
-                    for (int g = 0; g < 4; ++g) {
-                        const int j = g * kHid + u;
-                        float acc = n.b_ih[j] + n.b_hh[j];
-                        for (int i = 0; i < kKp; ++i) acc = fmaf(gate_w(w, j, i), xh[i], acc);
-                        pre[g] = acc;
-                    }
+                    host_gates(w, xh, u, pre);
                     float cv = fresh ? 0.0f : c[u];
                     hn[u] = cell_forward(pre[0], pre[1], pre[2], pre[3], &cv, gt);
                     c[u] = cv;
@@ -1497,9 +1493,7 @@ ha_status ha_host_lstm_seq_forward(int64_t n_nets, int64_t L, int64_t B, const f
 
 ha_status ha_host_lstm_seq_backward(int64_t n_nets, int64_t L, int64_t B, const uint8_t* episode_starts,
                                     const ha_lstm_seq_bwd* nets) {
-    ha_status st = check_seq(n_nets, L, B);
-    if (st != HE_OK) return st;
-    st = check_seq_bwd(n_nets, episode_starts, nets, 0u);
+    const ha_status st = check_seq_bwd(n_nets, L, B, episode_starts, nets, 0u);
     if (st != HE_OK) return st;
     std::vector<float> dgv(kGates);
     float* dg = dgv.data();
@@ -1544,10 +1538,9 @@ ha_status ha_lstm_seq_weight_grads(int64_t n_nets, int64_t L, int64_t B, const f
                                    const uint8_t* episode_starts, const ha_lstm_seq_wgrad* nets, void* workspace,
                                    void* stream) {
     ha_status st = check_wgrad(n_nets, L, B, x, episode_starts, nets, 15u);
+    if (st == HE_OK) st = check_workspace(workspace);
     if (st != HE_OK) return st;
-    if (bad_ptr(workspace, 15u)) return fail_to(nullptr, HE_EINVAL, "workspace must be non-NULL and 16-byte aligned");
-    WgradParams p;
-    memset(&p, 0, sizeof p);
+    WgradParams p = {};
     for (int64_t k = 0; k < n_nets; ++k) p.net[k] = nets[k];
     p.R = L * B;
     p.B = B;
@@ -1555,13 +1548,11 @@ ha_status ha_lstm_seq_weight_grads(int64_t n_nets, int64_t L, int64_t B, const f
     p.x = x;
     p.start = episode_starts;
     p.ws = (double*)workspace;
-    hipLaunchKernelGGL(lstm_wgrad_kernel, dim3((unsigned)p.n_chunks, kGates / kHid, (unsigned)n_nets), dim3(kThreads), 0,
-                       (hipStream_t)stream, p);
-    if (hipGetLastError() != hipSuccess) return fail_to(nullptr, HE_EHIP, "lstm_wgrad_kernel launch failed");
-    hipLaunchKernelGGL(lstm_wgrad_reduce_kernel, dim3((unsigned)((kWgPartial + 255) / 256), (unsigned)n_nets), dim3(256),
-                       0, (hipStream_t)stream, p);
-    if (hipGetLastError() != hipSuccess) return fail_to(nullptr, HE_EHIP, "lstm_wgrad_reduce_kernel launch failed");
-    return HE_OK;
+    st = launch(nullptr, lstm_wgrad_kernel, dim3((unsigned)p.n_chunks, kGates / kHid, (unsigned)n_nets), dim3(kThreads),
+                stream, "lstm_wgrad_kernel", p);
+    if (st != HE_OK) return st;
+    return launch(nullptr, lstm_wgrad_reduce_kernel, dim3((unsigned)((kWgPartial + 255) / 256), (unsigned)n_nets),
+                  dim3(256), stream, "lstm_wgrad_reduce_kernel", p);
 }
 
 ha_status ha_host_lstm_seq_weight_grads(int64_t n_nets, int64_t L, int64_t B, const float* x,

@@ -21,14 +21,13 @@ sums of d_gates over the L B rows: blocked torch GEMMs by default (weight_grads)
 weight_grads="kernel" libhedgeactor's lstm_wgrad_kernel (lstm_seq_weight_grads, contract W1-W4).
 """
 import ctypes
-import io
-import zipfile
+import functools
 
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _lib
-from .agent import ACT_DIM, HIDDEN, MLP, OBS_DIM, POLICY_KEYS, STATE_NAMES, _normalization, load
+from .agent import (ACT_DIM, HIDDEN, MLP, OBS_DIM, POLICY_KEYS, STATE_NAMES, _check, _normalization, _read_sb3_zip,
+                    load)
 
 _VP = ctypes.c_void_p
 NET_INPUTS = ("h0", "c0", "w_ih", "w_hh", "b_ih", "b_hh")   # lstm_sequence's per-network arguments
@@ -56,14 +55,6 @@ def _weight_grads_mode(mode):
     return mode
 
 
-def _check(lib, status, what):
-    if status != _lib.HE_OK:
-        msg = (lib.ha_policy_last_error(None) or b"").decode()
-        if status in (_lib.HE_ESHAPE, _lib.HE_EINVAL):
-            raise ValueError(f"{what}: {msg}")
-        raise _lib.HedgeEnvError(f"{what} failed (status {status}): {msg}")
-
-
 def _f32(t, shape, name, device):
     """t as a contiguous, 16-byte aligned float32 tensor of `shape` on `device` (no copy when it is)."""
     if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or t.device != device:
@@ -87,119 +78,83 @@ def _stream(device):
     return _raw_stream(device.index if device.index is not None else torch.cuda.current_device())
 
 
-def _workspace(lib, n, device):
-    return torch.empty(lib.ha_lstm_seq_workspace_bytes(n), dtype=torch.uint8, device=device)
+@functools.lru_cache(maxsize=16)
+def _seq_shapes(L, B):
+    """Every tensor of the three ha_lstm_seq_* structs by field name.  Cached (an update calls with one
+    L, B again and again) and therefore shared: read only."""
+    G = 4 * HIDDEN
+    return dict(w_ih=(G, OBS_DIM), w_hh=(G, HIDDEN), b_ih=(G,), b_hh=(G,), h0=(B, HIDDEN), c0=(B, HIDDEN),
+                h=(L, B, HIDDEN), c=(L, B, HIDDEN), gates=(L, B, 4, HIDDEN), d_h=(L, B, HIDDEN),
+                d_gates=(L, B, 4, HIDDEN), d_w_ih=(G, OBS_DIM), d_w_hh=(G, HIDDEN), d_b=(G,))
+
+
+def _seq_call(op, struct, x, like, episode_starts, nets, host, inputs, outputs,
+              workspace="ha_lstm_seq_workspace_bytes"):
+    """What lstm_seq_forward / _backward / _weight_grads share: ha_<op> on a HIP device or ha_host_<op>
+    (host; default: by the tensors' device) over `nets`, one or two dicts with the tensors `inputs` of
+    `struct`.  L, B are `like`'s leading dimensions; x is None for the call that takes none; `workspace`
+    names the entry point that sizes the device call's workspace, from as many of (n, L, B) as it takes.
+    -> per network the tuple of its new `outputs` tensors."""
+    lib = load()
+    dev = like.device
+    host = dev.type == "cpu" if host is None else bool(host)
+    if host != (dev.type == "cpu"):
+        raise ValueError("host=True takes CPU tensors, host=False tensors on a HIP device")
+    if x is not None and (x.dim() != 3 or x.shape[2] != OBS_DIM):
+        raise ValueError(f"x must be [L, B, {OBS_DIM}]")
+    L, B = int(like.shape[0]), int(like.shape[1])
+    shapes = _seq_shapes(L, B)
+    # (x, es, keep: the aligned copies live until the call is enqueued)
+    if x is not None:
+        x = _f32(x, (L, B, OBS_DIM), "x", dev)
+    es = _starts(episode_starts, L, B, dev)
+    lead = (es.data_ptr(),) if x is None else (x.data_ptr(), es.data_ptr())
+    n = len(nets)
+    arr = (struct * max(n, 1))()
+    keep, out = [], []
+    for k, net in enumerate(nets[:2]):
+        s = arr[k]
+        for name in inputs:
+            t = _f32(net[name], shapes[name], name, dev)
+            keep.append(t)
+            setattr(s, name, t.data_ptr())
+        new = tuple([torch.empty(shapes[name], dtype=torch.float32, device=dev) for name in outputs])
+        for name, t in zip(outputs, new):
+            setattr(s, name, t.data_ptr())
+        out.append(new)
+    if host:
+        st = getattr(lib, "ha_host_" + op)(n, L, B, *lead, arr)
+    else:
+        with torch.cuda.device(dev):
+            size = getattr(lib, workspace)   # sized by n alone, or by n, L, B
+            ws = torch.empty(size(n) if len(size.argtypes) == 1 else size(n, L, B), dtype=torch.uint8, device=dev)
+            st = getattr(lib, "ha_" + op)(n, L, B, *lead, arr, ws.data_ptr(), _stream(dev))
+    _check(lib, st, "ha_" + op)
+    return out
 
 
 def lstm_seq_forward(x, episode_starts, nets, host=None):
     """ha_lstm_seq_forward (ha_host_lstm_seq_forward with host=True; default: by x's device).
     x [L,B,13] f32, episode_starts [L,B] u8 / bool, nets: one or two dicts of NET_INPUTS tensors ->
     a list of (h [L,B,128], c [L,B,128], gates [L,B,4,128]) per network.  No autograd."""
-    lib = load()
-    dev = x.device
-    host = dev.type == "cpu" if host is None else bool(host)
-    if host != (dev.type == "cpu"):
-        raise ValueError("host=True takes CPU tensors, host=False tensors on a HIP device")
-    if x.dim() != 3 or x.shape[2] != OBS_DIM:
-        raise ValueError(f"x must be [L, B, {OBS_DIM}]")
-    L, B = int(x.shape[0]), int(x.shape[1])
-    x = _f32(x, (L, B, OBS_DIM), "x", dev)
-    es = _starts(episode_starts, L, B, dev)
-    n = len(nets)
-    arr = (HaLstmSeqNet * max(n, 1))()
-    keep, out = [x, es], []   # (keep: the aligned copies live until the call is enqueued)
-    shapes = dict(h0=(B, HIDDEN), c0=(B, HIDDEN), w_ih=(4 * HIDDEN, OBS_DIM), w_hh=(4 * HIDDEN, HIDDEN),
-                  b_ih=(4 * HIDDEN,), b_hh=(4 * HIDDEN,))
-    for k, net in enumerate(nets[:2]):
-        for name in NET_INPUTS:
-            t = _f32(net[name], shapes[name], name, dev)
-            keep.append(t)
-            setattr(arr[k], name, t.data_ptr())
-        h = torch.empty((L, B, HIDDEN), dtype=torch.float32, device=dev)
-        c = torch.empty((L, B, HIDDEN), dtype=torch.float32, device=dev)
-        gates = torch.empty((L, B, 4, HIDDEN), dtype=torch.float32, device=dev)
-        arr[k].h, arr[k].c, arr[k].gates = h.data_ptr(), c.data_ptr(), gates.data_ptr()
-        out.append((h, c, gates))
-    if host:
-        st = lib.ha_host_lstm_seq_forward(n, L, B, x.data_ptr(), es.data_ptr(), arr)
-    else:
-        with torch.cuda.device(dev):
-            ws = _workspace(lib, n, dev)
-            st = lib.ha_lstm_seq_forward(n, L, B, x.data_ptr(), es.data_ptr(), arr, ws.data_ptr(), _stream(dev))
-    _check(lib, st, "ha_lstm_seq_forward")
-    return out
+    return _seq_call("lstm_seq_forward", HaLstmSeqNet, x, x, episode_starts, nets, host, NET_INPUTS,
+                     ("h", "c", "gates"))
 
 
 def lstm_seq_backward(episode_starts, nets, host=None):
     """ha_lstm_seq_backward: nets = one or two dicts of w_hh [512,128], c0 [B,128], c [L,B,128], gates
     [L,B,4,128], d_h [L,B,128] -> a list of d_gates [L,B,4,128] per network.  No autograd."""
-    lib = load()
-    first = nets[0]["d_h"]
-    dev = first.device
-    host = dev.type == "cpu" if host is None else bool(host)
-    if host != (dev.type == "cpu"):
-        raise ValueError("host=True takes CPU tensors, host=False tensors on a HIP device")
-    L, B = int(first.shape[0]), int(first.shape[1])
-    es = _starts(episode_starts, L, B, dev)
-    n = len(nets)
-    arr = (HaLstmSeqBwd * max(n, 1))()
-    shapes = dict(w_hh=(4 * HIDDEN, HIDDEN), c0=(B, HIDDEN), c=(L, B, HIDDEN), gates=(L, B, 4, HIDDEN),
-                  d_h=(L, B, HIDDEN))
-    keep, out = [es], []
-    for k, net in enumerate(nets[:2]):
-        for name, shape in shapes.items():
-            t = _f32(net[name], shape, name, dev)
-            keep.append(t)
-            setattr(arr[k], name, t.data_ptr())
-        dg = torch.empty((L, B, 4, HIDDEN), dtype=torch.float32, device=dev)
-        arr[k].d_gates = dg.data_ptr()
-        out.append(dg)
-    if host:
-        st = lib.ha_host_lstm_seq_backward(n, L, B, es.data_ptr(), arr)
-    else:
-        with torch.cuda.device(dev):
-            ws = _workspace(lib, n, dev)
-            st = lib.ha_lstm_seq_backward(n, L, B, es.data_ptr(), arr, ws.data_ptr(), _stream(dev))
-    _check(lib, st, "ha_lstm_seq_backward")
-    return out
+    out = _seq_call("lstm_seq_backward", HaLstmSeqBwd, None, nets[0]["d_h"], episode_starts, nets, host,
+                    ("w_hh", "c0", "c", "gates", "d_h"), ("d_gates",))
+    return [dg for dg, in out]
 
 
 def lstm_seq_weight_grads(x, episode_starts, nets, host=None):
     """ha_lstm_seq_weight_grads (contract W1-W4): x [L,B,13], episode_starts [L,B], nets = one or two
     dicts of d_gates [L,B,4,128], h [L,B,128] (the forward's), h0 [B,128] -> a list of (d_w_ih [512,13],
     d_w_hh [512,128], d_b [512]) f32 per network; d_b is db_ih and db_hh.  No autograd."""
-    lib = load()
-    dev = x.device
-    host = dev.type == "cpu" if host is None else bool(host)
-    if host != (dev.type == "cpu"):
-        raise ValueError("host=True takes CPU tensors, host=False tensors on a HIP device")
-    if x.dim() != 3 or x.shape[2] != OBS_DIM:
-        raise ValueError(f"x must be [L, B, {OBS_DIM}]")
-    L, B = int(x.shape[0]), int(x.shape[1])
-    x = _f32(x, (L, B, OBS_DIM), "x", dev)
-    es = _starts(episode_starts, L, B, dev)
-    n = len(nets)
-    arr = (HaLstmSeqWgrad * max(n, 1))()
-    shapes = dict(d_gates=(L, B, 4, HIDDEN), h=(L, B, HIDDEN), h0=(B, HIDDEN))
-    keep, out = [x, es], []
-    for k, net in enumerate(nets[:2]):
-        for name, shape in shapes.items():
-            t = _f32(net[name], shape, name, dev)
-            keep.append(t)
-            setattr(arr[k], name, t.data_ptr())
-        g = (torch.empty((4 * HIDDEN, OBS_DIM), dtype=torch.float32, device=dev),
-             torch.empty((4 * HIDDEN, HIDDEN), dtype=torch.float32, device=dev),
-             torch.empty(4 * HIDDEN, dtype=torch.float32, device=dev))
-        arr[k].d_w_ih, arr[k].d_w_hh, arr[k].d_b = (t.data_ptr() for t in g)
-        out.append(g)
-    if host:
-        st = lib.ha_host_lstm_seq_weight_grads(n, L, B, x.data_ptr(), es.data_ptr(), arr)
-    else:
-        with torch.cuda.device(dev):
-            ws = torch.empty(lib.ha_lstm_seq_weight_grads_workspace_bytes(n, L, B), dtype=torch.uint8, device=dev)
-            st = lib.ha_lstm_seq_weight_grads(n, L, B, x.data_ptr(), es.data_ptr(), arr, ws.data_ptr(), _stream(dev))
-    _check(lib, st, "ha_lstm_seq_weight_grads")
-    return out
+    return _seq_call("lstm_seq_weight_grads", HaLstmSeqWgrad, x, x, episode_starts, nets, host,
+                     ("d_gates", "h", "h0"), ("d_w_ih", "d_w_hh", "d_b"), "ha_lstm_seq_weight_grads_workspace_bytes")
 
 
 def weight_grads(d_gates, x, h, h0, episode_starts, rows=1 << 18, block=128):
@@ -233,10 +188,11 @@ def weight_grads(d_gates, x, h, h0, episode_starts, rows=1 << 18, block=128):
 
 
 class _LstmSeq(torch.autograd.Function):
-    """h of one or two networks over the same x and episode_starts; per network the six NET_INPUTS."""
+    """h of one or two networks over the same x and episode_starts; per network the six NET_INPUTS.
+    weight_grads ("torch" / "kernel", lstm_sequence's keyword) is how backward forms the weight gradients."""
 
     @staticmethod
-    def forward(ctx, host, x, episode_starts, *tensors):
+    def forward(ctx, host, weight_grads, x, episode_starts, *tensors):
         n = len(tensors) // len(NET_INPUTS)
         nets = [dict(zip(NET_INPUTS, tensors[6 * k:6 * k + 6])) for k in range(n)]
         out = lstm_seq_forward(x, episode_starts, nets, host=host)
@@ -244,7 +200,7 @@ class _LstmSeq(torch.autograd.Function):
         for net, (h, c, gates) in zip(nets, out):
             saved += [net["h0"], net["c0"], net["w_hh"], h, c, gates]
         ctx.save_for_backward(*saved)
-        ctx.host, ctx.n, ctx.weight_grads = host, n, "torch"
+        ctx.host, ctx.n, ctx.weight_grads = host, n, weight_grads
         return tuple(h for h, _, _ in out)
 
     @staticmethod
@@ -257,7 +213,7 @@ class _LstmSeq(torch.autograd.Function):
             d = torch.zeros_like(h) if d is None else d
             nets.append(dict(w_hh=w_hh, c0=c0, c=c, gates=gates, d_h=d))
         d_gates = lstm_seq_backward(es, nets, host=ctx.host)
-        grads = [None, None, None]
+        grads = [None, None, None, None]
         if ctx.weight_grads == "kernel":   # both networks in one call
             wg = lstm_seq_weight_grads(x, es, [dict(d_gates=dg, h=h, h0=h0)
                                                for (h0, c0, w_hh, h, c, gates), dg in zip(per, d_gates)], host=ctx.host)
@@ -269,20 +225,6 @@ class _LstmSeq(torch.autograd.Function):
         return tuple(grads)
 
 
-class _LstmSeqKernel(_LstmSeq):
-    """_LstmSeq with the weight gradients from ha_lstm_seq_weight_grads (weight_grads="kernel")."""
-
-    @staticmethod
-    def forward(ctx, host, x, episode_starts, *tensors):
-        out = _LstmSeq.forward(ctx, host, x, episode_starts, *tensors)
-        ctx.weight_grads = "kernel"
-        return out
-
-
-def _seq_op(weight_grads):
-    return _LstmSeqKernel if _weight_grads_mode(weight_grads) == "kernel" else _LstmSeq
-
-
 def lstm_sequence(x, episode_starts, h0, c0, w_ih, w_hh, b_ih, b_hh, host=None, weight_grads="torch"):
     """The LSTM (13 -> 128, one layer, torch's gate order) over x [L,B,13] from (h0, c0) [B,128], the
     state zeroed before every step where episode_starts [L,B] is set -> h [L,B,128], differentiable
@@ -292,14 +234,14 @@ def lstm_sequence(x, episode_starts, h0, c0, w_ih, w_hh, b_ih, b_hh, host=None, 
     f32 GEMMs added in f64), "kernel" with ha_lstm_seq_weight_grads (contract W1-W4: the same bits on
     the device and on the host build)."""
     host = x.device.type == "cpu" if host is None else bool(host)
-    return _seq_op(weight_grads).apply(host, x, episode_starts, h0, c0, w_ih, w_hh, b_ih, b_hh)[0]
+    return _LstmSeq.apply(host, _weight_grads_mode(weight_grads), x, episode_starts, h0, c0, w_ih, w_hh, b_ih, b_hh)[0]
 
 
 def lstm_sequence_pair(x, episode_starts, actor, critic, host=None, weight_grads="torch"):
     """lstm_sequence for actor and critic in one launch each way: `actor`, `critic` are the NET_INPUTS
     tuples (h0, c0, w_ih, w_hh, b_ih, b_hh) -> (h_pi, h_vf)."""
     host = x.device.type == "cpu" if host is None else bool(host)
-    return _seq_op(weight_grads).apply(host, x, episode_starts, *actor, *critic)
+    return _LstmSeq.apply(host, _weight_grads_mode(weight_grads), x, episode_starts, *actor, *critic)
 
 
 # --------------------------------------------------------------------------- the policy as a torch module
@@ -370,9 +312,7 @@ class RecurrentPPOModule(torch.nn.Module):
     @classmethod
     def from_sb3_zip(cls, path, normalization=None, **kw):
         """An SB3 `model.save()` zip: its policy.pth is a plain torch state dict."""
-        with zipfile.ZipFile(path) as z:
-            sd = torch.load(io.BytesIO(z.read("policy.pth")), map_location="cpu", weights_only=True)
-        return cls.from_state_dict(sd, normalization=normalization, **kw)
+        return cls.from_state_dict(_read_sb3_zip(path), normalization=normalization, **kw)
 
     @classmethod
     def from_policy(cls, policy, device=None, weight_grads="torch"):

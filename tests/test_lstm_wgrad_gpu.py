@@ -146,7 +146,7 @@ def test_the_default_is_unchanged():
     grads = []
     for call in (lambda m, a, c: train.lstm_sequence_pair(x, es, a, c, weight_grads=m.weight_grads),
                  lambda m, a, c: train.lstm_sequence_pair(x, es, a, c),
-                 lambda m, a, c: train._LstmSeq.apply(False, x, es, *a, *c)):
+                 lambda m, a, c: train._LstmSeq.apply(False, "torch", x, es, *a, *c)):
         m = train.RecurrentPPOModule.from_policy(policy(kind), device=DEV)
         h = call(m, (nets[0]["h0"], nets[0]["c0"], *m.lstm_actor.tensors()),
                  (nets[1]["h0"], nets[1]["c0"], *m.lstm_critic.tensors()))
