@@ -13,6 +13,9 @@ reference's Python interface on top:
 * `lstm_sequence`, `lstm_sequence_pair`, `RecurrentPPOModule`, `ppo_update` -- the LSTM over a stored
   sequence with per-step resets as a differentiable op (one forward and one backward kernel for actor
   and critic), evaluate_actions and RecurrentPPO.train's loss on top of it (train.py)
+* `DeviceAdam` -- the gradient-norm clip and Adam's step over all parameters in two launches
+  (train.py); `RecurrentPolicy.load_device_state_dict` re-packs the policy from device tensors in one
+  launch (agent.py): a training iteration without a host round trip
 """
 __version__ = "0.1.0"
 
@@ -33,7 +36,7 @@ def __getattr__(name):
     if name == "RolloutCollector":
         from .collect import RolloutCollector
         return RolloutCollector
-    if name in ("lstm_sequence", "lstm_sequence_pair", "RecurrentPPOModule", "ppo_update"):
+    if name in ("lstm_sequence", "lstm_sequence_pair", "RecurrentPPOModule", "ppo_update", "DeviceAdam"):
         from . import train
         return getattr(train, name)
     raise AttributeError(name)

@@ -71,7 +71,10 @@ EXPORTS = ["ha_version", "ha_last_error", "ha_create", "ha_destroy", "ha_step", 
            "ha_policy_last_error", "ha_policy_create", "ha_policy_destroy", "ha_policy_update", "ha_policy_step",
            "ha_gae", "ha_host_policy_step", "ha_host_gae", "ha_lstm_seq_workspace_bytes", "ha_lstm_seq_forward",
            "ha_lstm_seq_backward", "ha_host_lstm_seq_forward", "ha_host_lstm_seq_backward",
-           "ha_lstm_seq_weight_grads_workspace_bytes", "ha_lstm_seq_weight_grads", "ha_host_lstm_seq_weight_grads"]
+           "ha_lstm_seq_weight_grads_workspace_bytes", "ha_lstm_seq_weight_grads", "ha_host_lstm_seq_weight_grads",
+           "ha_policy_refresh", "ha_policy_download", "ha_adam_workspace_bytes", "ha_adam_step", "ha_host_adam_step"]
+POLICY_TENSOR_FLOATS = sum(int(np.prod(shape)) for _, _, shape in POLICY_KEYS)   # HA_POLICY_TENSOR_FLOATS
+assert POLICY_TENSOR_FLOATS == 171461
 
 _F = ctypes.POINTER(ctypes.c_float)
 _D = ctypes.POINTER(ctypes.c_double)
@@ -135,6 +138,11 @@ def load(path=LIB_PATH):
         "ha_lstm_seq_weight_grads_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64]),
         "ha_lstm_seq_weight_grads": (i32, [i64, i64, i64] + [vp] * 5),
         "ha_host_lstm_seq_weight_grads": (i32, [i64, i64, i64] + [vp] * 3),
+        "ha_policy_refresh": (i32, [vp, PW, vp]),
+        "ha_policy_download": (i32, [vp, vp, vp]),
+        "ha_adam_workspace_bytes": (ctypes.c_size_t, [i64, vp]),
+        "ha_adam_step": (i32, [i64, vp, vp, vp, vp]),
+        "ha_host_adam_step": (i32, [i64, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -446,26 +454,84 @@ class RecurrentPolicy(_Recurrent):
     weights: {field: array} (policy_weights_from_state_dict) or a state dict.  obs_mean / obs_var,
     clip_obs, epsilon, activation: as RecurrentActor; leave the statistics out when the env is a
     DeviceVecNormalize, whose obs are normalised already.  The four LSTM states live on the device
-    as h_pi, c_pi, h_vf, c_vf [n, 128]."""
+    as h_pi, c_pi, h_vf, c_vf [n, 128].  After a PPO update the new tensors come in through
+    load_state_dict (host arrays or tensors, waits for the device) or load_device_state_dict (device
+    tensors, one launch on the stream)."""
 
     _struct, _abi, _keys = HaPolicyWeights, HA_POLICY_ABI_VERSION, POLICY_KEYS
     _fields_of = staticmethod(policy_weights_from_state_dict)
     _states = STATE_NAMES
     _create, _destroy, _last_error = "ha_policy_create", "ha_policy_destroy", "ha_policy_last_error"
+    _host_stale = False
 
     def __init__(self, weights, obs_mean=None, obs_var=None, clip_obs=10.0, epsilon=1e-8, activation="tanh",
                  device="cuda:0"):
         super().__init__(weights, obs_mean, obs_var, clip_obs, epsilon, activation, device)
+        self._host_stale = False   # load_device_state_dict ran: self._arrays are older than the handle's tensors
 
     def load_state_dict(self, sd):
         """New tensors (a state dict or {field: array}) after a PPO update: ha_policy_update re-packs
         and re-uploads them into the existing handle.  Waits for the device; the LSTM states stay."""
         self._set_tensors(sd)
+        self._host_stale = False   # all 21 host copies are new, and ha_policy_update uploads them
         if self._h is not None:
             import torch
             with torch.cuda.device(self.device):
                 st = self.lib.ha_policy_update(self._h, ctypes.byref(self._w))
             _check(self.lib, st, "ha_policy_update", self._h, "ha_policy_last_error")
+
+    def load_device_state_dict(self, sd):
+        """load_state_dict without the host: sd (a state dict such as module.state_dict(), or {field:
+        tensor}) holds contiguous float32 tensors on the policy's device, and ha_policy_refresh re-packs
+        them into the handle with one launch on the current stream.  Returns without waiting: a step
+        enqueued afterwards on that stream runs the new tensors, and the tensors may change again once
+        the call has returned only in work enqueued behind it.  Statistics, activation and the LSTM
+        states stay.  ValueError (and the handle as it was) for a missing key, a wrong shape or dtype,
+        a tensor that is not contiguous or not on the device.  The host copies (host_step,
+        RecurrentPPOModule.from_policy) follow on demand: _host_weights."""
+        h = self._handle()
+        torch = _torch
+        dotted = any("." in k for k in sd)
+        w = type(self._w).from_buffer_copy(self._w)
+        for key, field, shape in self._keys:
+            name = key if dotted else field
+            t = sd.get(name)
+            if t is None:
+                raise ValueError(f"state dict has no {name!r}")
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape \
+                    or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape} on {self.device}, not "
+                                 f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} on "
+                                 f"{getattr(t, 'device', 'the host')}")
+            setattr(w, field, ctypes.cast(ctypes.c_void_p(t.data_ptr()), _F))
+        st = self.lib.ha_policy_refresh(h, ctypes.byref(w), self._stream())
+        _check(self.lib, st, "ha_policy_refresh", h, "ha_policy_last_error")
+        self._host_stale = True
+
+    def _host_weights(self):
+        """(the weights struct, the arrays it points into) for whatever reads the tensors on the host.
+        After load_device_state_dict the first call downloads the handle's copy of the tensors the refresh
+        read (ha_policy_download: the one wait, on the current stream); later calls cost nothing."""
+        if self._host_stale:
+            flat = np.empty(POLICY_TENSOR_FLOATS, np.float32)
+            with _torch.cuda.device(self.device):
+                st = self.lib.ha_policy_download(self._h, flat.ctypes.data, self._stream())
+            _check(self.lib, st, "ha_policy_download", self._h, "ha_policy_last_error")
+            arrays, o = {}, 0
+            for _, field, shape in self._keys:   # POLICY_KEYS is in ha_policy_weights' order
+                n = int(np.prod(shape))
+                arrays[field] = flat[o:o + n].reshape(shape)
+                o += n
+            self._set_tensors(arrays)
+            self._host_stale = False
+        return self._w, self._arrays
+
+    def close(self):
+        try:
+            if self._h is not None and self._host_stale:
+                self._host_weights()   # the handle holds the only copy of the current tensors
+        finally:
+            super().close()
 
     @property
     def states(self):
@@ -550,7 +616,8 @@ class RecurrentPolicy(_Recurrent):
             raise ValueError("states is (h_pi, c_pi, h_vf, c_vf)")
         obs, es, n = self._host_inputs(obs, episode_start, STATE_NAMES, states)
         res = {name: np.empty((n,) + tail, np.float32) for name, tail in STEP_OUTPUTS}
-        st = self.lib.ha_host_policy_step(ctypes.byref(self._w), n, int(env_id_offset), int(seed) & (2 ** 64 - 1),
+        w, _ = self._host_weights()
+        st = self.lib.ha_host_policy_step(ctypes.byref(w), n, int(env_id_offset), int(seed) & (2 ** 64 - 1),
                                           int(step_index), int(bool(deterministic)), int(bool(write_state)),
                                           obs.ctypes.data, es.ctypes.data, *(a.ctypes.data for a in states),
                                           *(res[name].ctypes.data for name, _ in STEP_OUTPUTS))

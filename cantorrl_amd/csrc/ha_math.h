@@ -160,4 +160,41 @@ HE_HD void gae_env(int64_t e, int64_t n, int64_t K, float g32, float gl32, const
     }
 }
 
+// ---------------------------------------------------------------- the optimizer step (ha_adam_step)
+// the constants of contract O4-O5, formed once on the host
+struct AdamConsts {
+    float b1, b2, a1, a2, ss, bc2s, eps, max_norm;
+    int clip;
+};
+
+// Contract O3-O4: the norm from the f64 total, the coefficient every gradient is multiplied by
+HE_HD float adam_clip(double total, const AdamConsts& k, float* norm_out) {
+    const float norm = (float)sqrt(total);
+    *norm_out = norm;
+    if (!k.clip) return 1.0f;
+    const float d = norm + 1e-6f;
+    const float q = k.max_norm / d;
+    return q < 1.0f ? q : 1.0f;
+}
+
+// Contract O5 for one element: one f32 rounding per line
+HE_HD void adam_element(float g, float c, const AdamConsts& k, float* p, float* m, float* v) {
+    const float gc = g * c;
+    const float m1 = k.b1 * *m;
+    const float m2 = k.a1 * gc;
+    const float mn = m1 + m2;
+    const float gg = gc * gc;
+    const float v1 = k.b2 * *v;
+    const float v2 = k.a2 * gg;
+    const float vn = v1 + v2;
+    const float sq = sqrtf(vn);
+    const float sb = sq / k.bc2s;
+    const float den = sb + k.eps;
+    const float r = mn / den;
+    const float u = k.ss * r;
+    *m = mn;
+    *v = vn;
+    *p = *p - u;
+}
+
 }  // namespace ha

@@ -26,7 +26,8 @@
 // stage the same obs; registers and LDS stay at actor_kernel's figures.  gae_kernel (ha_gae) is
 // one thread per env over [K][n] arrays.  lstm_seq_fwd_kernel / lstm_seq_bwd_kernel (the PPO update's
 // LSTM over a stored sequence, forward and backward) and lstm_wgrad_kernel / lstm_wgrad_reduce_kernel
-// (its weight gradients) are described where they stand.
+// (its weight gradients), policy_pack_kernel (ha_policy_refresh) and opt_norm_kernel / opt_adam_kernel
+// (ha_adam_step) are described where they stand.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -328,8 +329,9 @@ struct ha_actor {
 
 struct ha_policy {
     char err[256];
-    void* blob;       // both packed networks, log_std / std, the statistics
+    void* blob;       // both packed networks, log_std / std, the statistics, then the tensors of the last refresh
     PolicyParams p;
+    bool refreshed;   // ha_policy_refresh has run since the last create / update: the blob's tail is current
 };
 
 namespace {
@@ -1178,6 +1180,171 @@ ha_status check_wgrad(int64_t n_nets, int64_t L, int64_t B, const void* x, const
     return HE_OK;
 }
 
+// ---------------------------------------------------------------- a policy's blob from device tensors
+// policy_pack_kernel (ha_policy_refresh): pack_policy's layout written from the 21 tensors where they
+// stand on the device, grid-stride over the blob's floats up to the statistics; then the tensors
+// themselves, flat in ha_policy_weights' order, behind the blob (ha_policy_download).
+constexpr int kPolicyTensors = 21;
+constexpr size_t kSnapFloats = HA_POLICY_TENSOR_FLOATS;
+constexpr int kTensorFloats[kPolicyTensors] = {
+    kGates * kObs, kGates * kHid, kGates, kGates, kMlp * kHid, kMlp, kMlp * kMlp, kMlp, kAct * kMlp, kAct, kAct,
+    kGates * kObs, kGates * kHid, kGates, kGates, kMlp * kHid, kMlp, kMlp * kMlp, kMlp, kMlp, 1};
+
+struct PolicyPackParams {
+    const float* t[kPolicyTensors];   // w_ih w_hh b_ih b_hh w1 b1 w2 b2 w3 b3 log_std, then the critic's ten
+    int32_t off[kPolicyTensors + 1];  // where each begins in the flat copy
+    float* blob;
+    float* snap;
+};
+
+// float `i` of one packed network (pack_net's layout) from its tensors in torch layout
+HE_HD float packed_net_float(unsigned i, const float* __restrict__ w_ih,
+                                                  const float* __restrict__ w_hh, const float* __restrict__ b_ih,
+                                                  const float* __restrict__ b_hh, const float* __restrict__ w1,
+                                                  const float* __restrict__ b1, const float* __restrict__ w2,
+                                                  const float* __restrict__ b2, const float* __restrict__ w3,
+                                                  const float* __restrict__ b3, unsigned n_out) {
+    if (i < o_bg) {
+        const int g = i & 3, l = (i >> 2) & 63;
+        const int rest = i >> 8, ug = rest / kStepsG, s = rest - ug * kStepsG;
+        const int j = g * kHid + ug * 32 + (l & 31), k = 2 * s + (l >> 5);
+        return k < kObs ? w_ih[j * kObs + k] : (k < kKx ? w_hh[j * kHid + (k - kObs)] : 0.0f);
+    }
+    if (i < o_w1) return b_ih[i - o_bg] + b_hh[i - o_bg];
+    if (i < o_b1) {
+        const unsigned q = i - o_w1, l = q & 63, rt = q >> 12, s = (q >> 6) & (kHid / 2 - 1);
+        return w1[(rt * 32 + (l & 31)) * kHid + 2 * s + (l >> 5)];
+    }
+    if (i < o_w2) return b1[i - o_b1];
+    if (i < o_b2) {
+        const unsigned q = i - o_w2, l = q & 63, rt = q >> 11, s = (q >> 6) & (kMlp / 2 - 1);
+        return w2[(rt * 32 + (l & 31)) * kMlp + 2 * s + (l >> 5)];
+    }
+    if (i < o_w3) return b2[i - o_b2];
+    if (i < o_b3) return i - o_w3 < n_out * kMlp ? w3[i - o_w3] : 0.0f;
+    return i - o_b3 < n_out ? b3[i - o_b3] : 0.0f;
+}
+static_assert(kHid / 2 == 64 && kMlp / 2 == 32, "the shifts of packed_net_float");
+
+__global__ __launch_bounds__(256) void policy_pack_kernel(const PolicyPackParams p) {
+    const unsigned first = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
+    for (unsigned idx = first; idx < o_ls + 2 * kAct; idx += stride) {
+        float v;
+        if (idx < kNetFloats)
+            v = packed_net_float(idx, p.t[0], p.t[1], p.t[2], p.t[3], p.t[4], p.t[5], p.t[6], p.t[7], p.t[8], p.t[9], kAct);
+        else if (idx < o_ls)
+            v = packed_net_float(idx - kNetFloats, p.t[11], p.t[12], p.t[13], p.t[14], p.t[15], p.t[16], p.t[17],
+                                 p.t[18], p.t[19], p.t[20], 1);
+        else
+            v = idx < o_ls + kAct ? p.t[10][idx - o_ls] : policy_std(p.t[10][idx - o_ls - kAct]);
+        p.blob[idx] = v;
+    }
+#pragma unroll
+    for (int k = 0; k < kPolicyTensors; ++k) {
+        const float* __restrict__ src = p.t[k];
+        float* dst = p.snap + p.off[k];
+        const unsigned n = p.off[k + 1] - p.off[k];
+        for (unsigned i = first; i < n; i += stride) dst[i] = src[i];
+    }
+}
+
+// ---------------------------------------------------------------- the optimizer step (contract O1-O5)
+// opt_norm_kernel: one workgroup per block of 256 elements, the f64 tree of O1 in LDS, s_b to the
+// workspace.  opt_adam_kernel: the same grid; every thread adds the s_b in order (the same loads and
+// adds in every lane of every workgroup: the same bits), then updates its element.  The tensors and
+// the first block of each travel in the kernel's arguments.
+struct AdamParams {
+    ha_adam_tensor t[HA_OPT_MAX_TENSORS];
+    int32_t first[HA_OPT_MAX_TENSORS + 1];   // first[k]: the first block of tensor k; first[n]: all blocks
+    int32_t n;
+    AdamConsts k;
+    double* partial;
+    float* norm_out;
+};
+
+// the tensor of block b: the last k with first[k] <= b (wave-uniform)
+__device__ __forceinline__ int adam_tensor_of(const AdamParams& p, int b) {
+    int k = 0;
+    while (k + 1 < p.n && p.first[k + 1] <= b) ++k;
+    return k;
+}
+
+__global__ __launch_bounds__(HA_OPT_BLOCK) void opt_norm_kernel(const AdamParams p) {
+    __shared__ double q[HA_OPT_BLOCK];
+    const int b = blockIdx.x, tid = threadIdx.x, k = adam_tensor_of(p, b);
+    const int64_t i = (int64_t)(b - p.first[k]) * HA_OPT_BLOCK + tid;
+    const float g = i < p.t[k].numel ? p.t[k].grad[i] : 0.0f;
+    q[tid] = (double)g * (double)g;
+    for (int off = HA_OPT_BLOCK / 2; off >= 1; off >>= 1) {
+        __syncthreads();
+        if (tid < off) q[tid] = q[tid] + q[tid + off];
+    }
+    if (tid == 0) p.partial[b] = q[0];
+}
+
+__global__ __launch_bounds__(HA_OPT_BLOCK) void opt_adam_kernel(const AdamParams p) {
+    const int b = blockIdx.x, tid = threadIdx.x, k = adam_tensor_of(p, b);
+    const int nb = p.first[p.n];
+    const double* __restrict__ partial = p.partial;
+    double total = 0.0;
+    for (int j = 0; j < nb; ++j) total = total + partial[j];
+    float norm;
+    const float c = adam_clip(total, p.k, &norm);
+    if (b == 0 && tid == 0 && p.norm_out) *p.norm_out = norm;
+    const int64_t i = (int64_t)(b - p.first[k]) * HA_OPT_BLOCK + tid;
+    if (i >= p.t[k].numel) return;
+    float pv = p.t[k].param[i], m = p.t[k].exp_avg[i], v = p.t[k].exp_avg_sq[i];
+    adam_element(p.t[k].grad[i], c, p.k, &pv, &m, &v);
+    p.t[k].param[i] = pv;
+    p.t[k].exp_avg[i] = m;
+    p.t[k].exp_avg_sq[i] = v;
+}
+
+// The checks of ha_adam_step / ha_host_adam_step; fills first[] and the constants (hy and k NULL: the
+// shapes alone, for the workspace's size).
+ha_status check_adam(int64_t n, const ha_adam_tensor* ts, const ha_adam_hyper* hy, int32_t* first, AdamConsts* k) {
+    char m[200];
+    if (n < 1 || n > HA_OPT_MAX_TENSORS) {
+        snprintf(m, sizeof m, "n_tensors = %lld: 1 to %d tensors a call", (long long)n, HA_OPT_MAX_TENSORS);
+        return fail_to(nullptr, HE_ESHAPE, m);
+    }
+    if (!ts) return fail_to(nullptr, HE_EINVAL, "tensors is NULL");
+    int64_t blocks = 0;
+    for (int64_t j = 0; j < n; ++j) {
+        if (ts[j].numel < 1) {
+            snprintf(m, sizeof m, "tensor %lld has numel %lld", (long long)j, (long long)ts[j].numel);
+            return fail_to(nullptr, HE_ESHAPE, m);
+        }
+        first[j] = (int32_t)blocks;
+        blocks += (ts[j].numel - 1) / HA_OPT_BLOCK + 1;
+        if (blocks > HA_OPT_MAX_BLOCKS) {
+            snprintf(m, sizeof m, "more than %d blocks of %d elements in one call", HA_OPT_MAX_BLOCKS, HA_OPT_BLOCK);
+            return fail_to(nullptr, HE_ESHAPE, m);
+        }
+    }
+    first[n] = (int32_t)blocks;
+    if (!hy) return k ? fail_to(nullptr, HE_EINVAL, "hyper is NULL") : HE_OK;   // (the workspace's size needs none)
+    for (int64_t j = 0; j < n; ++j)
+        if (!ts[j].param || !ts[j].grad || !ts[j].exp_avg || !ts[j].exp_avg_sq)
+            return fail_to(nullptr, HE_EINVAL, "a tensor pointer is NULL");
+    const double inf = __builtin_inf();
+    if (hy->t < 1) return fail_to(nullptr, HE_EINVAL, "t is the 1-based step count");
+    if (!(hy->lr > -inf && hy->lr < inf) || !(hy->eps >= 0.0 && hy->eps < inf))
+        return fail_to(nullptr, HE_EINVAL, "lr must be finite, eps finite and >= 0");
+    if (!(hy->beta1 >= 0.0 && hy->beta1 < 1.0) || !(hy->beta2 >= 0.0 && hy->beta2 < 1.0))
+        return fail_to(nullptr, HE_EINVAL, "beta1 and beta2 must be in [0, 1)");
+    k->b1 = (float)hy->beta1;
+    k->b2 = (float)hy->beta2;
+    k->a1 = (float)(1.0 - hy->beta1);
+    k->a2 = (float)(1.0 - hy->beta2);
+    k->ss = (float)(hy->lr / (1.0 - pow(hy->beta1, (double)hy->t)));
+    k->bc2s = (float)sqrt(1.0 - pow(hy->beta2, (double)hy->t));
+    k->eps = (float)hy->eps;
+    k->clip = hy->max_grad_norm > 0.0 && hy->max_grad_norm < inf;
+    k->max_norm = k->clip ? (float)hy->max_grad_norm : 0.0f;
+    return HE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1284,7 +1451,7 @@ ha_status ha_policy_create(const ha_policy_weights* w, ha_policy** out) {
     *out = nullptr;
     ha_status st = check_policy_weights(w, nullptr);
     if (st != HE_OK) return st;
-    std::vector<float> hbuf(kPolicyFloats, 0.0f);
+    std::vector<float> hbuf(kPolicyFloats + kSnapFloats, 0.0f);   // the tail: ha_policy_refresh's copy of the tensors
     pack_policy(w, hbuf.data());
     st = create_handle(hbuf, out);
     if (st == HE_OK) policy_params(w, (const float*)(*out)->blob, &(*out)->p);
@@ -1308,7 +1475,45 @@ ha_status ha_policy_update(ha_policy* policy, const ha_policy_weights* w) {
     if (hipDeviceSynchronize() != hipSuccess) return fail(policy, HE_EHIP, "hipDeviceSynchronize failed");
     st = upload_blob(hbuf, &policy->blob, policy->err);
     if (st == HE_OK) policy_params(w, (const float*)policy->blob, &policy->p);
+    policy->refreshed = false;
     return st;
+}
+
+ha_status ha_policy_refresh(ha_policy* policy, const ha_policy_weights* w_dev, void* stream) {
+    if (!policy) return HE_EINVAL;
+    ha_policy_weights w;   // the statistics are the handle's: the pointers of w_dev are not looked at
+    if (w_dev) {
+        w = *w_dev;
+        w.obs_mean = w.obs_var = nullptr;
+    }
+    ha_status st = check_policy_weights(w_dev ? &w : nullptr, policy);
+    if (st != HE_OK) return st;
+    PolicyPackParams p;
+    const float* t[kPolicyTensors] = {w.w_ih,   w.w_hh,   w.b_ih,   w.b_hh,   w.w1, w.b1,  w.w2, w.b2,  w.w3, w.b3, w.log_std,
+                                      w.c_w_ih, w.c_w_hh, w.c_b_ih, w.c_b_hh, w.v1, w.vb1, w.v2, w.vb2, w.v3, w.vb3};
+    p.off[0] = 0;
+    for (int k = 0; k < kPolicyTensors; ++k) {
+        if (((uintptr_t)t[k]) & 3u) return fail(policy, HE_EINVAL, "the tensors must be 4-byte aligned");
+        p.t[k] = t[k];
+        p.off[k + 1] = p.off[k] + kTensorFloats[k];
+    }
+    p.blob = (float*)policy->blob;
+    p.snap = p.blob + kPolicyFloats;
+    st = launch(policy->err, policy_pack_kernel, dim3(512), dim3(256), stream, "policy_pack_kernel", p);
+    if (st == HE_OK) policy->refreshed = true;
+    return st;
+}
+
+ha_status ha_policy_download(ha_policy* policy, float* out, void* stream) {
+    if (!policy) return HE_EINVAL;
+    if (!out) return fail(policy, HE_EINVAL, "out is NULL");
+    if (!policy->refreshed)
+        return fail(policy, HE_ESTATE, "no ha_policy_refresh since the handle's tensors last came from the host");
+    if (hipMemcpyAsync(out, (const float*)policy->blob + kPolicyFloats, kSnapFloats * sizeof(float),
+                       hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
+        hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
+        return fail(policy, HE_EHIP, "download of the refreshed tensors failed");
+    return HE_OK;
 }
 
 ha_status ha_policy_step(ha_policy* policy, int64_t n, int64_t env_id_offset, uint64_t seed, uint64_t step_index,
@@ -1594,6 +1799,66 @@ ha_status ha_host_lstm_seq_weight_grads(int64_t n_nets, int64_t L, int64_t B, co
             for (int j = 0; j < kHid; ++j) n.d_w_hh[u * kHid + j] = (float)tv[(size_t)u * kKp + kObs + j];
             n.d_b[u] = (float)tv[(size_t)u * kKp + kKx];
         }
+    }
+    return HE_OK;
+}
+
+size_t ha_adam_workspace_bytes(int64_t n_tensors, const ha_adam_tensor* tensors) {
+    int32_t first[HA_OPT_MAX_TENSORS + 1];
+    if (check_adam(n_tensors, tensors, nullptr, first, nullptr) != HE_OK) return 0;
+    return (size_t)first[n_tensors] * sizeof(double);
+}
+
+ha_status ha_adam_step(int64_t n_tensors, const ha_adam_tensor* tensors, const ha_adam_hyper* hyper, void* workspace,
+                       void* stream) {
+    AdamParams p;
+    ha_status st = check_adam(n_tensors, tensors, hyper, p.first, &p.k);
+    if (st != HE_OK) return st;
+    if (!workspace || (((uintptr_t)workspace) & 7u))
+        return fail_to(nullptr, HE_EINVAL, "workspace must be non-NULL and 8-byte aligned");
+    uintptr_t bits = (uintptr_t)hyper->grad_norm_out;
+    for (int64_t j = 0; j < n_tensors; ++j) {
+        p.t[j] = tensors[j];
+        bits |= (uintptr_t)tensors[j].param | (uintptr_t)tensors[j].grad | (uintptr_t)tensors[j].exp_avg |
+                (uintptr_t)tensors[j].exp_avg_sq;
+    }
+    if (bits & 3u) return fail_to(nullptr, HE_EINVAL, "the tensors and grad_norm_out must be 4-byte aligned");
+    for (int64_t j = n_tensors; j < HA_OPT_MAX_TENSORS; ++j) {
+        p.t[j] = ha_adam_tensor{nullptr, nullptr, nullptr, nullptr, 0};
+        p.first[j + 1] = p.first[n_tensors];
+    }
+    p.n = (int32_t)n_tensors;
+    p.partial = (double*)workspace;
+    p.norm_out = hyper->grad_norm_out;
+    const dim3 grid((unsigned)p.first[n_tensors]), block(HA_OPT_BLOCK);
+    st = launch(nullptr, opt_norm_kernel, grid, block, stream, "opt_norm_kernel", p);
+    if (st != HE_OK) return st;
+    return launch(nullptr, opt_adam_kernel, grid, block, stream, "opt_adam_kernel", p);
+}
+
+ha_status ha_host_adam_step(int64_t n_tensors, const ha_adam_tensor* tensors, const ha_adam_hyper* hyper) {
+    int32_t first[HA_OPT_MAX_TENSORS + 1];
+    AdamConsts k;
+    const ha_status st = check_adam(n_tensors, tensors, hyper, first, &k);
+    if (st != HE_OK) return st;
+    double total = 0.0;   // O1, O2
+    for (int64_t j = 0; j < n_tensors; ++j)
+        for (int64_t i0 = 0; i0 < tensors[j].numel; i0 += HA_OPT_BLOCK) {
+            double q[HA_OPT_BLOCK];
+            for (int i = 0; i < HA_OPT_BLOCK; ++i) {
+                const float g = i0 + i < tensors[j].numel ? tensors[j].grad[i0 + i] : 0.0f;
+                q[i] = (double)g * (double)g;
+            }
+            for (int off = HA_OPT_BLOCK / 2; off >= 1; off >>= 1)
+                for (int i = 0; i < off; ++i) q[i] = q[i] + q[i + off];
+            total = total + q[0];
+        }
+    float norm;   // O3, O4
+    const float c = adam_clip(total, k, &norm);
+    if (hyper->grad_norm_out) *hyper->grad_norm_out = norm;
+    for (int64_t j = 0; j < n_tensors; ++j) {   // O5
+        const ha_adam_tensor& t = tensors[j];
+        for (int64_t i = 0; i < t.numel; ++i) adam_element(t.grad[i], c, k, t.param + i, t.exp_avg + i, t.exp_avg_sq + i);
     }
     return HE_OK;
 }

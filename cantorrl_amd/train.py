@@ -12,6 +12,10 @@ top of it, in torch.
         stats = ppo_update(module, opt, buf, envs_per_batch=1024)
         policy.load_state_dict(module.state_dict())
 
+With opt = DeviceAdam(module.parameters(), lr=1e-4, eps=1e-5) the clip and the optimizer step are
+libhedgeactor's ha_adam_step (two launches, contract O1-O5), and policy.load_device_state_dict(
+module.state_dict()) re-packs the policy on the device: an iteration without a host round trip.
+
 Only the LSTM is a kernel: nn.LSTM has no per-step reset, so sb3_contrib's _process_sequence runs one
 LSTM call per time step, forward and again in autograd's backward.  Here a workgroup walks all L
 steps of its 32 envs inside one launch, actor and critic side by side.  The MLPs, the heads, the
@@ -317,7 +321,7 @@ class RecurrentPPOModule(torch.nn.Module):
     @classmethod
     def from_policy(cls, policy, device=None, weight_grads="torch"):
         """The tensors, activation and statistics of an agent.RecurrentPolicy, on its device."""
-        a = policy._arrays
+        _, a = policy._host_weights()   # after a load_device_state_dict: the tensors it read
         m = cls(activation=policy.activation, obs_mean=a.get("obs_mean"), obs_var=a.get("obs_var"),
                 clip_obs=policy.clip_obs, epsilon=policy.epsilon, weight_grads=weight_grads)
         m.load_state_dict({k: torch.from_numpy(a[f].copy()) for k, f, _ in POLICY_KEYS})
@@ -372,6 +376,122 @@ def ppo_loss(values, log_prob, entropy, old_log_prob, advantages, returns, clip_
     return loss, stats
 
 
+class HaAdamTensor(ctypes.Structure):
+    _fields_ = [(k, _VP) for k in ("param", "grad", "exp_avg", "exp_avg_sq")] + [("numel", ctypes.c_int64)]
+
+
+class HaAdamHyper(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in ("lr", "beta1", "beta2", "eps", "max_grad_norm")] + \
+               [("t", ctypes.c_int64), ("grad_norm_out", _VP)]
+
+
+OPT_BLOCK, OPT_MAX_TENSORS, OPT_MAX_BLOCKS = 256, 64, 4096   # HA_OPT_* of include/hedge_actor.h
+
+
+class DeviceAdam(torch.optim.Optimizer):
+    """torch.optim.Adam (no weight decay, no amsgrad) with the gradient-norm clip in front, as
+    libhedgeactor's ha_adam_step: two launches for all the parameters, arithmetic contract O1-O5 of
+    include/hedge_actor.h, the same bits from the host build (CPU parameters run ha_host_adam_step).
+
+        opt = DeviceAdam(module.parameters(), lr=1e-4, eps=1e-5)
+        loss.backward()
+        grad_norm = opt.clip_and_step(0.5)     # clip_grad_norm_(params, 0.5) + Adam.step()
+
+    One parameter group of up to 64 contiguous float32 tensors on one device, 2^20 elements in blocks
+    of 256.  param_groups[0]["lr"] is read at every step (schedulers work); state_dict() has
+    torch.optim.Adam's layout (step, exp_avg, exp_avg_sq per parameter) and loads into one, and back.
+    Nothing synchronises with the host."""
+
+    _prep = None   # what does not change from step to step (_prepare); not part of the pickled state
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+        if not 0.0 <= lr or not 0.0 <= eps or not all(0.0 <= b < 1.0 for b in betas):
+            raise ValueError(f"DeviceAdam: lr {lr} and eps {eps} must be >= 0, betas {betas} in [0, 1)")
+        # torch.optim.Adam's keys, so that either optimizer runs a state dict of the other
+        defaults = dict(torch.optim.Adam([torch.zeros(1)]).defaults, lr=lr, betas=tuple(betas), eps=eps)
+        super().__init__(params, defaults)
+        load()              # a missing library is an error here, not at the first step
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._prep = None   # new state tensors
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        self._prep = None
+
+    def _prepare(self):
+        """The parameters checked, their state made, the ctypes array with everything but the gradients
+        filled in, the workspace -> (params, array, step counters, device, workspace)."""
+        if len(self.param_groups) != 1:
+            raise ValueError("DeviceAdam runs one parameter group")
+        params = self.param_groups[0]["params"]
+        if not 1 <= len(params) <= OPT_MAX_TENSORS:
+            raise ValueError(f"DeviceAdam takes 1 to {OPT_MAX_TENSORS} parameters, not {len(params)}")
+        arr = (HaAdamTensor * len(params))()
+        dev, steps = params[0].device, []
+        for a, p in zip(arr, params):
+            st = self.state[p]
+            if not st:
+                st["step"] = torch.zeros((), dtype=torch.float32)   # on the host, as torch.optim.Adam keeps it
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            for what, x in (("parameter", p), ("state exp_avg", st["exp_avg"]), ("state exp_avg_sq", st["exp_avg_sq"])):
+                if x.dtype != torch.float32 or not x.is_contiguous() or x.device != dev or x.shape != p.shape:
+                    raise ValueError(f"DeviceAdam: every {what} must be a contiguous float32 tensor on {dev}")
+            if st["step"].device.type != "cpu":   # a fused torch.optim.Adam's: reading it each step would wait
+                st["step"] = st["step"].detach().to("cpu", torch.float32)
+            steps.append(st["step"])
+            a.exp_avg, a.exp_avg_sq, a.numel = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
+        if len({int(s) for s in steps}) != 1:
+            raise ValueError(f"DeviceAdam: the parameters' step counts differ ({sorted({int(s) for s in steps})})")
+        ws = None
+        if dev.type != "cpu":
+            size = load().ha_adam_workspace_bytes(len(params), arr)
+            if not size:
+                _check(load(), load().ha_adam_step(len(params), arr, None, None, None), "ha_adam_step")   # says why
+            ws = torch.empty(size, dtype=torch.uint8, device=dev)
+        self._prep = (params, arr, steps, dev, ws)
+        return self._prep
+
+    @torch.no_grad()
+    def clip_and_step(self, max_grad_norm):
+        """clip_grad_norm_(params, max_grad_norm) and Adam's step; max_grad_norm None, <= 0 or inf: no
+        clip.  -> the gradients' norm before the clip, a scalar tensor on the parameters' device."""
+        params, arr, steps, dev, ws = self._prep or self._prepare()
+        group = self.param_groups[0]
+        if group["weight_decay"] or group["amsgrad"] or group["maximize"]:
+            raise ValueError("DeviceAdam has no weight_decay, amsgrad or maximize")
+        f32 = torch.float32
+        for a, p in zip(arr, params):   # the gradients are new tensors after every zero_grad(set_to_none=True)
+            g = p.grad
+            if g is None:
+                raise ValueError("DeviceAdam: a parameter has no gradient (every tensor of the call is updated)")
+            if g.dtype != f32 or g.device != dev or not g.is_contiguous():
+                raise ValueError(f"DeviceAdam: every gradient must be a contiguous float32 tensor on {dev}")
+            a.param, a.grad = p.data_ptr(), g.data_ptr()
+        norm = torch.empty((), dtype=f32, device=dev)
+        hy = HaAdamHyper(float(group["lr"]), float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]),
+                         0.0 if max_grad_norm is None else float(max_grad_norm), int(steps[0]) + 1, norm.data_ptr())
+        if dev.type == "cpu":
+            st = load().ha_host_adam_step(len(params), arr, ctypes.byref(hy))
+        else:
+            with torch.cuda.device(dev):
+                st = load().ha_adam_step(len(params), arr, ctypes.byref(hy), ws.data_ptr(), _stream(dev))
+        _check(load(), st, "ha_adam_step")
+        torch._foreach_add_(steps, 1)
+        return norm
+
+    def step(self, closure=None):
+        """Adam's step without a clip."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self.clip_and_step(None)
+        return loss
+
+
 def minibatch(buffer, idx, k0, k1):
     """Envs `idx` (an int64 tensor) x steps [k0, k1) of a RolloutBuffer -> a dict of contiguous tensors
     and states0, the LSTM states before step k0."""
@@ -393,7 +513,9 @@ def ppo_update(module, optimizer, buffer, *, n_epochs=10, envs_per_batch=None, w
     envs_per_batch (default: all), each group x each time window one optimizer step.  window=None: the
     whole K steps from buffer.h_pi ...; window=W (dividing K): W steps from buffer.states[k0], which
     collect(states=True) stores.  Defaults: the reference's default_hpo_params (train_ppo_v2.py:601-605:
-    clip_range 0.3, ent_coef 1e-5, vf_coef 0.5, max_grad_norm 0.5, n_epochs 10).  Nothing synchronises
+    clip_range 0.3, ent_coef 1e-5, vf_coef 0.5, max_grad_norm 0.5, n_epochs 10).  An optimizer with a
+    clip_and_step method (DeviceAdam) clips and steps through it, any other through clip_grad_norm_ and
+    step().  Nothing synchronises
     with the host; returns the last minibatch's statistics and the mean loss as device scalars."""
     K, n = buffer.k_steps, buffer.n_envs
     W = K if window is None else int(window)
@@ -419,8 +541,11 @@ def ppo_update(module, optimizer, buffer, *, n_epochs=10, envs_per_batch=None, w
                                        clip_range, ent_coef, vf_coef, normalize_advantage)
                 optimizer.zero_grad(set_to_none=True)
                 loss.backward()
-                stats["grad_norm"] = torch.nn.utils.clip_grad_norm_(params, max_grad_norm)
-                optimizer.step()
+                if hasattr(optimizer, "clip_and_step"):   # DeviceAdam: the clip and the step in two launches
+                    stats["grad_norm"] = optimizer.clip_and_step(max_grad_norm)
+                else:
+                    stats["grad_norm"] = torch.nn.utils.clip_grad_norm_(params, max_grad_norm)
+                    optimizer.step()
                 total = stats["loss"] if total is None else total + stats["loss"]
                 count += 1
     if count:

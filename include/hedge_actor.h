@@ -4,8 +4,9 @@
  * Linear 2) evaluated for N device-resident envs in one HIP kernel on MI355X (gfx950), the
  * per-episode sums of a closed-loop evaluation around he_step, and the training side: actor,
  * critic, action sampling and log-probability of a rollout step in one launch, GAE, and for the
- * PPO update both LSTMs over a stored sequence with per-step resets, forward and backward, and
- * their weight gradients.
+ * PPO update both LSTMs over a stored sequence with per-step resets, forward and backward, their
+ * weight gradients, the gradient-norm clip with Adam's step, and the re-packing of a policy's handle
+ * from the updated device tensors.
  *
  * Conventions (as hedge_env.h): plain C types, every entry point returns an ha_status (the
  * he_status values), the last failure's message is ha_last_error(handle), no C++ exception
@@ -101,6 +102,30 @@
  *   W4. outputs, each rounded once from f64 to f32: d_w_ih[u][k] = total[u][k] for k < 13,
  *       d_w_hh[u][j] = total[u][13 + j], d_b[u] = total[u][141] (the value of db_ih and db_hh).
  *   Nothing in W1-W4 depends on the grid, the CU count or the number of networks per call.
+ *
+ * The optimizer step (ha_adam_step: torch.nn.utils.clip_grad_norm_ over every tensor of the call, then
+ * torch.optim.Adam's step without weight decay and amsgrad; restated).  The tensors t = 0 .. n - 1 of
+ * the call in the caller's order, g the gradient, m = exp_avg, v = exp_avg_sq, p the parameter:
+ *   O1. sum of squares per block: each tensor is cut into blocks of HA_OPT_BLOCK = 256 consecutive
+ *       elements, a short last block padded with +0.  Element i of a block contributes q_i =
+ *       f64(g_i) f64(g_i) (exact in f64); the 256 values are added in f64 by a fixed tree: q_i +=
+ *       q_(i + 128) for i < 128, then q_i += q_(i + 64) for i < 64, ... q_0 += q_1.  s_b = q_0.
+ *   O2. total = the f64 sum from 0.0 of s_b over the blocks in (tensor, block) order.
+ *   O3. norm = f32(sqrt(total)), the f64 square root correctly rounded, then rounded to f32.
+ *   O4. with a clip (max_grad_norm > 0 and finite): q = f32(max_grad_norm) / (norm + 1e-6f) in f32,
+ *       c = q < 1 ? q : 1.  Without: c = 1.  g' = g c, one f32 multiply (by 1 where nothing clips, as
+ *       torch multiplies).
+ *   O5. per element in f32, every operation rounded once, no fmaf, no contraction, in the order
+ *       written; b1 = f32(beta1), b2 = f32(beta2), a1 = f32(1 - beta1), a2 = f32(1 - beta2), ss =
+ *       f32(lr / (1 - beta1^t)), bc2s = f32(sqrt(1 - beta2^t)), e = f32(eps), each formed on the host
+ *       in f64 (pow, sqrt of libm) and rounded once, t the 1-based count of this step:
+ *         m <- (b1 m) + (a1 g')
+ *         v <- (b2 v) + (a2 (g' g'))
+ *         denom = (sqrtf(v) / bc2s) + e
+ *         p <- p - (ss (m / denom))
+ *       f32 / and sqrtf are correctly rounded on the device (-fhip-fp32-correctly-rounded-divide-sqrt).
+ *   Nothing in O1-O5 depends on the grid; a tensor cut at a multiple of 256 elements into two tensors
+ *   standing where it stood gives the same blocks, hence the same bits.
  */
 #ifndef HEDGE_ACTOR_H
 #define HEDGE_ACTOR_H
@@ -250,6 +275,27 @@ ha_status ha_policy_destroy(ha_policy* policy);
  * step in flight reads half-written weights, and copies synchronously.  Not capturable. */
 ha_status ha_policy_update(ha_policy* policy, const ha_policy_weights* w);
 
+/* The 21 tensors of a policy, flat: w_ih ... log_std, c_w_ih ... vb3 in ha_policy_weights' order. */
+#define HA_POLICY_TENSOR_FLOATS 171461
+
+/* ha_policy_update's re-packing from DEVICE tensors, on the stream: the 21 tensor pointers of w_dev
+ * are DEVICE pointers (f32, torch layout, 4-byte aligned; an optimizer's parameters as they stand
+ * when the launch runs).  One launch of policy_pack_kernel writes the handle's packed networks, b_ih +
+ * b_hh (one f32 add), log_std and std = f32(exp_f64(log_std)): bit for bit what ha_policy_update
+ * uploads for the same values.  The same launch copies the 21 tensors into a buffer of the handle
+ * (ha_policy_download).  obs_mean / obs_var of w_dev are ignored: statistics, clip, epsilon and
+ * activation stay as ha_policy_create or the last ha_policy_update set them; the other fields are
+ * checked as ha_policy_create checks them (HE_ESHAPE, HE_EINVAL; a NULL handle or tensor HE_EINVAL),
+ * before the launch.  Stream-ordered: no host synchronisation, no copy call, no allocation, capturable.
+ * A step enqueued later on the same stream reads the new tensors, one enqueued earlier the old; work
+ * on OTHER streams that reads the handle or writes the tensors is the caller's to order (an event). */
+ha_status ha_policy_refresh(ha_policy* policy, const ha_policy_weights* w_dev, void* stream);
+
+/* The tensors the last ha_policy_refresh read, to HOST memory: out [HA_POLICY_TENSOR_FLOATS], flat in
+ * ha_policy_weights' order.  Copies on `stream` and WAITS for that stream.  HE_ESTATE when no refresh
+ * has run since ha_policy_create or the last ha_policy_update (the caller's host tensors are current). */
+ha_status ha_policy_download(ha_policy* policy, float* out, void* stream);
+
 /* One collection step of n envs (contract P1-P6), one launch, DEVICE pointers, no host
  * synchronisation.  obs [n][13], episode_start [n] u8; h_pi, c_pi, h_vf, c_vf [n][128] are
  * updated in place (16-byte aligned) unless write_state = 0, which computes every output and
@@ -362,6 +408,46 @@ ha_status ha_lstm_seq_weight_grads(int64_t n_nets, int64_t L, int64_t B, const f
 /* The same arithmetic on the host, HOST pointers (no alignment asked), no workspace. */
 ha_status ha_host_lstm_seq_weight_grads(int64_t n_nets, int64_t L, int64_t B, const float* x,
                                         const uint8_t* episode_starts, const ha_lstm_seq_wgrad* nets);
+
+/* ---- the optimizer step: gradient-norm clip + Adam over a list of tensors (O1-O5) ---- */
+#define HA_OPT_BLOCK 256         /* elements of one block of O1 */
+#define HA_OPT_MAX_TENSORS 64
+#define HA_OPT_MAX_BLOCKS 4096   /* blocks of one call: 2^20 elements in whole blocks; the policy's 21
+                                    tensors make 677.  Every workgroup adds all the blocks' sums (O2). */
+
+/* One tensor of the call: numel f32 elements each, contiguous.  grad is read, never written. */
+typedef struct ha_adam_tensor {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t numel;
+} ha_adam_tensor;
+
+typedef struct ha_adam_hyper {
+    double lr, beta1, beta2, eps;
+    double max_grad_norm; /* <= 0, +inf or NaN: no clip */
+    int64_t t;            /* the 1-based count of this step: the host knows it without reading the device */
+    float* grad_norm_out; /* [1] or NULL: norm of O3, before the clip, as clip_grad_norm_ returns it */
+} ha_adam_hyper;
+
+/* Bytes of ha_adam_step's workspace: one f64 per block, the s_b of O1.  0 for a list the call
+ * refuses.  The workspace carries nothing from call to call. */
+size_t ha_adam_workspace_bytes(int64_t n_tensors, const ha_adam_tensor* tensors);
+
+/* O1-O5 over `tensors`, a HOST array of structs of DEVICE pointers (4-byte aligned; the workspace 8):
+ * two launches, opt_norm_kernel with one workgroup per block writing s_b, then opt_adam_kernel, where
+ * every workgroup adds the s_b in O2's order (all of them get the same bits), updates its own block
+ * and the first writes grad_norm_out (a DEVICE pointer).  No atomics, no waiting between workgroups;
+ * stream-ordered, no host synchronisation, no allocation.  Before any launch: n_tensors outside
+ * [1, HA_OPT_MAX_TENSORS], a numel < 1 or more than HA_OPT_MAX_BLOCKS blocks in all is HE_ESHAPE; a
+ * NULL pointer, t < 1, lr or eps not finite, eps < 0 or a beta outside [0, 1) HE_EINVAL.  The message
+ * is ha_policy_last_error(NULL). */
+ha_status ha_adam_step(int64_t n_tensors, const ha_adam_tensor* tensors, const ha_adam_hyper* hyper, void* workspace,
+                       void* stream);
+
+/* The same arithmetic on the host, HOST pointers throughout, no workspace. */
+ha_status ha_host_adam_step(int64_t n_tensors, const ha_adam_tensor* tensors, const ha_adam_hyper* hyper);
 
 #ifdef __cplusplus
 }

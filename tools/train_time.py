@@ -6,6 +6,7 @@ autograd, f32.  And one ppo_update epoch over a buffer of the first shape.  HIP 
 call, warm-up first, the median.
 
     python tools/train_time.py [--reps R] [--out FILE.jsonl] [--shapes L,B ...] [--weight-grads torch|kernel|both]
+                               [--optimizer]
 
 --weight-grads torch (the default) times lstm_sequence_pair as it is called by default, its weight
 gradients from train.weight_grads.  kernel times forward plus backward with weight_grads="kernel", and
@@ -19,11 +20,20 @@ composition's saved activations, about 8 KB per step, env and network, still fit
 3 KB), and L = 32, B = 2 (the reference's BATCH_SIZE_AGENT = 32 steps of N_ENVS = 2).  One JSON line
 per shape; with --out they are appended to the file as well (profiles/train_time_*.jsonl).
 FLOP per env-step and network: 2 x 512 x 141 forward, 2 x 512 x 128 backward.
+
+--optimizer times, instead, the seam between two rollouts on the module's 21 tensors: clip_grad_norm_ +
+torch.optim.Adam.step() (default and fused=True) against train.DeviceAdam.clip_and_step (HIP events, and
+wall time to completion), RecurrentPolicy.load_state_dict against load_device_state_dict (wall time with
+the Python call included: until the call returns, and until the device is done), and one ppo_update
+epoch per --shapes entry with each optimizer.
 """
 import argparse
+import copy
 import json
 import os
+import statistics
 import sys
+import time
 
 import numpy as np
 import torch
@@ -139,6 +149,10 @@ def measure(L, B, reps, mode="torch"):
 
 
 def measure_update(m, K, n, per, reps):
+    return measure_update_with(m, torch.optim.Adam(m.parameters(), lr=1e-5, eps=1e-5), K, n, per, reps)
+
+
+def measure_update_with(m, opt, K, n, per, reps):
     buf = RolloutBuffer(K, n, DEV)
     g = torch.Generator(device=DEV).manual_seed(2)
     for name in ("observations", "actions", "rewards", "values", "advantages", "returns", "h_pi", "c_pi", "h_vf", "c_vf"):
@@ -146,9 +160,79 @@ def measure_update(m, K, n, per, reps):
         t.copy_(torch.randn(t.shape, device=DEV, generator=g) * 0.5)
     buf.log_probs.fill_(-1.0)
     buf.episode_starts.copy_((torch.rand((K, n), device=DEV, generator=g) < 0.004).to(torch.uint8))
-    opt = torch.optim.Adam(m.parameters(), lr=1e-5, eps=1e-5)
     us = median_us(lambda: train.ppo_update(m, opt, buf, n_epochs=1, envs_per_batch=per), reps, 1)
     return dict(ppo_update_epoch_us=round(us, 1), K=K, n_envs=n, envs_per_batch=per, minibatches=-(-n // per), update_reps=reps)
+
+
+def wall_us(fn, reps, warmup=3):
+    """Median wall time of fn() with the Python call included, the device idle before each call ->
+    (until the call returns, until the device has finished what it enqueued), microseconds."""
+    ret, done = [], []
+    for k in range(warmup + reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        t1 = time.perf_counter()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        if k >= warmup:
+            ret.append((t1 - t0) * 1e6)
+            done.append((t2 - t0) * 1e6)
+    return round(statistics.median(ret), 1), round(statistics.median(done), 1)
+
+
+def measure_optimizer(shapes, reps):
+    """--optimizer: (a) the clip and the optimizer step over the module's 21 tensors, torch's
+    clip_grad_norm_ + torch.optim.Adam.step() (default and fused=True) against DeviceAdam.clip_and_step,
+    HIP events; (b) RecurrentPolicy.load_state_dict against load_device_state_dict, wall time; and one
+    ppo_update epoch per shape and optimizer.  Every baseline runs in this process, beside what it is
+    compared with."""
+    from cantorrl_amd.agent import RecurrentPolicy
+    rng = np.random.default_rng(0)
+    m = module(rng)
+    r = dict(mode="optimizer", reps=reps, device=torch.cuda.get_device_name(0), tensors=len(list(m.parameters())),
+             floats=sum(p.numel() for p in m.parameters()))
+    g = torch.Generator(device=DEV).manual_seed(4)
+    makers = (("torch_adam", lambda ps: torch.optim.Adam(ps, lr=1e-5, eps=1e-5)),
+              ("torch_adam_fused", lambda ps: torch.optim.Adam(ps, lr=1e-5, eps=1e-5, fused=True)),
+              ("device_adam", lambda ps: train.DeviceAdam(ps, lr=1e-5, eps=1e-5)))
+    for name, make in makers:
+        mm = copy.deepcopy(m)
+        ps = list(mm.parameters())
+        for p in ps:
+            p.grad = torch.randn(p.shape, device=DEV, generator=g) * 0.1
+        opt = make(ps)
+
+        def torch_step():
+            torch.nn.utils.clip_grad_norm_(ps, 0.5)
+            opt.step()
+
+        fn = (lambda: opt.clip_and_step(0.5)) if name == "device_adam" else torch_step
+        r[f"clip_step_{name}_us"] = round(median_us(fn, reps, 3), 1)
+        r[f"clip_step_{name}_wall_us"] = wall_us(fn, reps)[1]
+    for base in ("torch_adam", "torch_adam_fused"):
+        r[f"device_adam_speedup_vs_{base}"] = round(r[f"clip_step_{base}_us"] / r["clip_step_device_adam_us"], 2)
+    # (b) the refresh: the module's tensors into a live policy handle
+    pol = RecurrentPolicy({k: v.detach().cpu().numpy() for k, v in m.state_dict().items()}, device=DEV)
+    pol.reset_states(2)
+    r["load_state_dict_return_us"], r["load_state_dict_done_us"] = wall_us(lambda: pol.load_state_dict(m.state_dict()), reps)
+    r["load_device_state_dict_return_us"], r["load_device_state_dict_done_us"] = wall_us(
+        lambda: pol.load_device_state_dict(m.state_dict()), reps)
+    r["refresh_device_us"] = round(median_us(lambda: pol.load_device_state_dict(m.state_dict()), reps, 3), 1)
+    r["refresh_speedup_done"] = round(r["load_state_dict_done_us"] / r["load_device_state_dict_done_us"], 2)
+    pol.close()
+    lines = [r]
+    for L, B in shapes:
+        u = dict(mode="optimizer_update", L=L, B=B, device=r["device"])
+        for name, make in makers:
+            mm = copy.deepcopy(m)
+            res = measure_update_with(mm, make(mm.parameters()), L, B, max(B // 4, 1), max(reps // 5, 3))
+            u[f"ppo_update_epoch_{name}_us"] = res.pop("ppo_update_epoch_us")
+            u.update(res)
+            del mm
+            torch.cuda.empty_cache()
+        lines.append(u)
+    return lines
 
 
 def main():
@@ -157,9 +241,14 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--out")
     ap.add_argument("--weight-grads", choices=("torch", "kernel", "both"), default="torch")
+    ap.add_argument("--optimizer", action="store_true",
+                    help="time the clip + optimizer step and the policy refresh against their baselines instead")
     a = ap.parse_args()
     lines = []
-    for k, s in enumerate(a.shapes):
+    if a.optimizer:
+        lines = [json.dumps(r) for r in measure_optimizer([tuple(int(v) for v in s.split(",")) for s in a.shapes], a.reps)]
+        print("\n".join(lines), flush=True)
+    for k, s in enumerate([] if a.optimizer else a.shapes):
         L, B = (int(v) for v in s.split(","))
         r, m = measure(L, B, a.reps, a.weight_grads)
         if k == 0 and a.weight_grads != "kernel":
