@@ -9,8 +9,9 @@ import copy
 import numpy as np
 import pytest
 
+import _ppo_reference as ref
 from test_lstm_seq_cpu import (ACTOR, BS, GRAD_NAMES, LS, PATTERNS, WEIGHTS, bits, d_h_for, host_backward, net_inputs, policy,
-                               seq_case)
+                               seq_case, torch_lstm_loop)
 from test_lstm_wgrad_cpu import BLOCK, CHUNK, T, host_wgrad, random_case, references
 from test_ppo_update_gpu import HYPER, loop_evaluate, rollout, states0
 
@@ -86,17 +87,18 @@ def test_autograd_on_the_device_within_4_d_ref():
         assert torch.equal(w[k][2].grad, w[k][3].grad)
 
 
-def minibatch_grads(m, buf, evaluate):
+def minibatch_grads(m, buf, evaluate, loss_fn=ref.loss):
     """The gradient RecurrentPPO.train takes for the whole buffer as one minibatch, in m's dtype, as f64,
-    BEFORE the gradient-norm clip.  The clip multiplies all 21 tensors by one coefficient whose rounding
+    BEFORE the gradient-norm clip; loss_fn: the restated loss for the reference side, train.ppo_loss for
+    the module under test.  The clip multiplies all 21 tensors by one coefficient whose rounding
     error is that of the largest tensor (action_net): after it a small tensor's distance from the f64
     restatement is the norm's error, not the tensor's own (measured: 14 x d_ref on value_net.bias,
     which no kernel touches, with either weight_grads mode), so the tensors are compared as they
     leave backward()."""
     dt = m.log_std.dtype
     v, lp, ent = evaluate(m)
-    loss, _ = train.ppo_loss(v, lp, ent, buf.log_probs.to(dt), buf.advantages.to(dt), buf.returns.to(dt),
-                             HYPER["clip_range"], HYPER["ent_coef"], HYPER["vf_coef"])
+    loss, _ = loss_fn(v, lp, ent, buf.log_probs.to(dt), buf.advantages.to(dt), buf.returns.to(dt),
+                      HYPER["clip_range"], HYPER["ent_coef"], HYPER["vf_coef"])
     m.zero_grad()
     loss.backward()
     return {k: p.grad.detach().to(torch.float64) for k, p in m.named_parameters()}
@@ -110,10 +112,23 @@ def test_one_minibatch_and_an_update_cycle_in_kernel_mode():
     def loop(mod):
         return loop_evaluate(mod, buf.observations, buf.actions, buf.episode_starts, states0(buf))
 
-    g32 = minibatch_grads(copy.deepcopy(m), buf, loop)
+    def loop_module_heads(mod):
+        """The restatement up to the LSTMs' outputs, then the module's own heads."""
+        x = ref.normalize(buf.observations, ref.constants(mod))
+        s = states0(buf)
+        h_pi = torch_lstm_loop(x, buf.episode_starts, s[0], s[1], *mod.lstm_actor.tensors())
+        h_vf = torch_lstm_loop(x, buf.episode_starts, s[2], s[3], *mod.lstm_critic.tensors())
+        return mod.heads(h_pi, h_vf, buf.actions)
+
+    # The f64 side is the restatement throughout (tests/_ppo_reference.py: its heads and its loss).  The
+    # f32 side, which only sizes the bound, keeps the module's heads over the all-torch LSTM loop: with
+    # the restated heads there too, d_ref of mlp_extractor.policy_net.0.bias (64 elements, one draw of
+    # f32 noise) came out at 9.5e-8 on an MI355X and this build's unchanged 3.95e-7 at 4.17 x d_ref.
+    # What the heads compute is held by test_ppo_loss_cpu.py and the replay tests.
+    g32 = minibatch_grads(copy.deepcopy(m), buf, loop_module_heads)
     g64 = minibatch_grads(copy.deepcopy(m).double(), buf, loop)
     got = minibatch_grads(m, buf, lambda mod: mod.evaluate_actions(buf.observations, buf.actions, buf.episode_starts,
-                                                                   states0(buf)))
+                                                                   states0(buf)), train.ppo_loss)
     torch.cuda.synchronize()
     assert len(got) == 21
     for k, g in got.items():

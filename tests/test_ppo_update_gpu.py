@@ -1,13 +1,14 @@
 """RecurrentPPOModule.evaluate_actions and ppo_update on the GPU, against what the RolloutCollector
-stored and against the all-torch f32 composition of the same module (its LSTM as sb3_contrib's
-Python loop of one cell per time step, test_lstm_seq_cpu.torch_lstm_loop).  Bounds are measured: the
-all-torch f32 composition's own error against the same reference, times 4 (as DESIGN 18 and 19)."""
+stored and against the all-torch f32 composition of the module's tensors (tests/_ppo_reference.py: the
+LSTM as sb3_contrib's Python loop of one cell per time step, the heads and the loss from their
+formulas).  Bounds are measured: the all-torch f32 composition's own error against the same
+reference, times 4 (as DESIGN 18 and 19)."""
 import copy
 
 import pytest
 
+import _ppo_reference as ref
 from test_actor_gpu import gbm_env
-from test_lstm_seq_cpu import torch_lstm_loop
 from test_policy_collect_cpu import critic_golden, make_policy
 
 torch = pytest.importorskip("torch")
@@ -22,13 +23,9 @@ HYPER = dict(clip_range=0.3, ent_coef=1e-5, vf_coef=0.5, max_grad_norm=0.5)
 
 
 def loop_evaluate(m, obs, actions, es, states0):
-    """evaluate_actions of module m (f32 or f64) from torch ops alone."""
-    dt = m.log_std.dtype
-    x = m.normalize_obs(obs).to(dt)
-    s = [t.to(dt) for t in states0]
-    h_pi = torch_lstm_loop(x, es, s[0], s[1], *m.lstm_actor.tensors())
-    h_vf = torch_lstm_loop(x, es, s[2], s[3], *m.lstm_critic.tensors())
-    return m.heads(h_pi, h_vf, actions.to(dt))
+    """evaluate_actions over module m's tensors (f32 or f64) from torch ops alone: the restatement, which
+    calls nothing of the module's."""
+    return ref.evaluate(dict(m.named_parameters()), ref.constants(m), obs, actions, es, states0)
 
 
 def rollout(n=33, K=16, states=True, seed=42):
@@ -69,8 +66,8 @@ def clipped_grads(m, buf):
     alone in m's dtype, after the gradient-norm clip."""
     dt = m.log_std.dtype
     v, lp, ent = loop_evaluate(m, buf.observations, buf.actions, buf.episode_starts, states0(buf))
-    loss, _ = train.ppo_loss(v, lp, ent, buf.log_probs.to(dt), buf.advantages.to(dt), buf.returns.to(dt),
-                             HYPER["clip_range"], HYPER["ent_coef"], HYPER["vf_coef"])
+    loss, _ = ref.loss(v, lp, ent, buf.log_probs.to(dt), buf.advantages.to(dt), buf.returns.to(dt),
+                       HYPER["clip_range"], HYPER["ent_coef"], HYPER["vf_coef"])
     m.zero_grad()
     loss.backward()
     torch.nn.utils.clip_grad_norm_(list(m.parameters()), HYPER["max_grad_norm"])
