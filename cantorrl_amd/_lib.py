@@ -2,12 +2,12 @@
 
 The shared library is built in-tree (`cantorrl_amd/lib/libhedgeenv.so`, see
 `cantorrl_amd/build.py`).  There is no fallback: if the library cannot be
-loaded, every constructor raises.  torch is imported first so that the HIP
-runtime torch ships (SONAME libamdhip64.so.7) is the one the library binds to
--- one runtime per process, so torch streams and data_ptr()s are valid here.
+loaded, every constructor raises (the loader itself is _bind.load).
 """
 import ctypes
 import os
+
+from . import _bind
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # CANTORRL_HEDGEENV_LIB: an alternative build (diagnostic / A-B builds under tools/ab/)
@@ -93,7 +93,6 @@ EPISODE_RECORD = _np.dtype([("env_id", "<i8"), ("length", "<i4"), ("reserved", "
                             ("per_share_pnl_sum", "<f8"), ("reserved2", "<f8")])
 assert EPISODE_RECORD.itemsize == 80
 
-_P = ctypes.c_void_p
 INFO_FIELDS = [
     ("step_pnl_total", "f8"), ("per_share_step_pnl", "f8"), ("raw_pnl_deviation_abs", "f8"),
     ("transaction_costs_total", "f8"), ("commission_cost", "f8"), ("slippage_cost", "f8"),
@@ -111,20 +110,7 @@ INFO_FIELDS = [
 
 
 class HeInfo(ctypes.Structure):
-    _fields_ = [(name, _P) for name, _ in INFO_FIELDS]
-
-
-EXPORTS = [
-    "he_config_init", "he_create", "he_destroy", "he_last_error", "he_version", "he_load_paths",
-    "he_seed", "he_reset", "he_reset_episodes", "he_step", "he_rollout", "he_num_envs", "he_episode_length",
-    "he_num_episodes", "he_get_config", "he_state_size", "he_get_state", "he_set_state",
-    "he_pcg64_seed_state", "he_host_episode_draws", "he_host_philox", "he_host_div_by", "he_host_div_byf", "he_time_next_step", "he_rollout_policy", "he_host_box_muller",
-    "he_sync_market", "he_vecnorm_stats_len", "he_vecnorm_scratch_bytes", "he_vecnorm_init", "he_vecnorm_step",
-    "he_vecnorm_apply", "he_vecnorm_attach", "he_vecnorm_attach_eval", "he_vecnorm_reset", "he_fixed_european_marks", "he_bs_delta_hedge", "he_count_nonfinite",
-    "he_device_rng", "he_device_math", "he_host_math", "he_episode_summaries", "he_host_alloc", "he_host_free",
-    "he_stream_wait", "he_step_signal", "he_signal_seq", "he_signal_wait", "he_host_episode_wrap",
-    "he_host_vecnorm_sb3",
-]
+    _fields_ = [(name, ctypes.c_void_p) for name, _ in INFO_FIELDS]
 
 
 class HeVecnormParams(ctypes.Structure):
@@ -153,6 +139,63 @@ class HeVecnormOut(ctypes.Structure):
         "stats", "returns", "obs_out", "reward_out", "terminal_obs_out", "ep_return", "ep_length", "ep_return_done",
         "ep_length_done")]
 
+_vp, _i32, _i64, _u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
+_cfgp, _infop, _vnp = ctypes.POINTER(HeConfig), ctypes.POINTER(HeInfo), ctypes.POINTER(HeVecnormParams)
+# every entry point of include/hedge_env.h: symbol -> (restype, argtypes)
+SIG = {
+    "he_config_init": (_i32, [_cfgp, _i32]),
+    "he_create": (_i32, [_cfgp, ctypes.POINTER(_vp)]),
+    "he_destroy": (_i32, [_vp]),
+    "he_last_error": (ctypes.c_char_p, [_vp]),
+    "he_version": (ctypes.c_char_p, []),
+    "he_load_paths": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64]),
+    "he_seed": (_i32, [_vp, _vp, _vp, _i64]),
+    "he_reset": (_i32, [_vp, _vp, _i64, _vp, _infop, _vp]),
+    "he_reset_episodes": (_i32, [_vp, _vp, _vp, _i64, _vp, _infop, _vp]),
+    "he_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _infop, _vp]),
+    "he_rollout": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "he_rollout_policy": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "he_num_envs": (_i64, [_vp]),
+    "he_episode_length": (_i32, [_vp]),
+    "he_num_episodes": (_i64, [_vp]),
+    "he_get_config": (_i32, [_vp, _cfgp]),
+    "he_state_size": (ctypes.c_size_t, [_vp]),
+    "he_get_state": (_i32, [_vp, _vp, ctypes.c_size_t]),
+    "he_set_state": (_i32, [_vp, _vp, ctypes.c_size_t]),
+    "he_pcg64_seed_state": (_i32, [_u64, ctypes.POINTER(ctypes.c_uint64 * 4)]),
+    "he_host_episode_draws": (_i32, [_u64, _u64, _i64, _vp]),
+    "he_host_philox": (_i32, [_u64, _u64, _u64, ctypes.POINTER(ctypes.c_uint32 * 4)]),
+    "he_host_div_by": (_i32, [_vp, _i64, ctypes.c_double, _vp]),
+    "he_host_div_byf": (_i32, [_vp, _i64, ctypes.c_float, _vp]),
+    "he_host_box_muller": (_i32, [_vp, _vp, _i64, _vp, _vp]),
+    "he_time_next_step": (_i32, [_vp, _vp, _vp]),
+    "he_sync_market": (_i32, [_vp, _vp]),
+    "he_vecnorm_stats_len": (_i64, [_i32]),
+    "he_vecnorm_scratch_bytes": (_i64, [_i64, _i32]),
+    "he_vecnorm_init": (_i32, [_vp, _i32, _vp]),
+    "he_vecnorm_step": (_i32, [_vnp, _i64] + [_vp] * 15 + [_vp]),
+    "he_vecnorm_apply": (_i32, [_vnp, _i64] + [_vp] * 15 + [_vp]),
+    "he_vecnorm_attach": (_i32, [_vp, _vnp, _vp, _vp, _vp]),
+    "he_vecnorm_attach_eval": (_i32, [_vp, _vnp, ctypes.POINTER(HeVecnormOut)]),
+    "he_vecnorm_reset": (_i32, [_vnp, _i64] + [_vp] * 5 + [_vp]),
+    "he_host_vecnorm_sb3": (_i32, [_vnp, _i64] + [_vp] * 9),
+    "he_fixed_european_marks": (_i32, [_vp, _i64, _i32, ctypes.c_double, _vp, _vp, _vp, _vp]),
+    "he_bs_delta_hedge": (_i32, [_vp, _i64, _i32, ctypes.c_double, ctypes.c_double, _vp, _vp]),
+    "he_count_nonfinite": (_i32, [_vp, _i64, _vp, _vp]),
+    "he_device_rng": (_i32, [_u64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "he_device_math": (_i32, [_i32, _vp, _i64, _vp, _vp]),
+    "he_host_math": (_i32, [_i32, _vp, _i64, _vp]),
+    "he_host_episode_wrap": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp]),
+    "he_episode_summaries": (_i32, [_vp, _vp, _vp]),
+    "he_host_alloc": (_i32, [ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "he_host_free": (_i32, [_vp]),
+    "he_stream_wait": (_i32, [_vp]),
+    "he_step_signal": (_i32, [_vp, _vp]),
+    "he_signal_seq": (ctypes.c_uint32, [_vp]),
+    "he_signal_wait": (_i32, [_vp, _vp, _vp]),
+}
+EXPORTS = list(SIG)
+
 _lib = None
 
 
@@ -161,81 +204,13 @@ class HedgeEnvError(RuntimeError):
 
 
 def load(path=LIB_PATH):
-    """Load libhedgeenv (once).  Raises if the in-tree library is missing."""
+    """Load libhedgeenv (once).  Raises if the in-tree library is missing.  A build from
+    another place (an A/B build of an older tree) may lack the newer entry points."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(path):
-        raise HedgeEnvError(
-            f"{path} not found: build it with `python -m cantorrl_amd.build` "
-            "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
-    try:
-        import torch  # noqa: F401  (bind to torch's HIP runtime, see module doc)
-    except ImportError:
-        pass
-    lib = ctypes.CDLL(path)
-    vp, i32, i64, u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
-    sig = {
-        "he_config_init": (i32, [ctypes.POINTER(HeConfig), i32]),
-        "he_create": (i32, [ctypes.POINTER(HeConfig), ctypes.POINTER(vp)]),
-        "he_destroy": (i32, [vp]),
-        "he_last_error": (ctypes.c_char_p, [vp]),
-        "he_version": (ctypes.c_char_p, []),
-        "he_load_paths": (i32, [vp, vp, vp, vp, vp, i64, i64]),
-        "he_seed": (i32, [vp, vp, vp, i64]),
-        "he_reset": (i32, [vp, vp, i64, vp, ctypes.POINTER(HeInfo), vp]),
-        "he_reset_episodes": (i32, [vp, vp, vp, i64, vp, ctypes.POINTER(HeInfo), vp]),
-        "he_step": (i32, [vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(HeInfo), vp]),
-        "he_rollout": (i32, [vp, i32, vp, vp, vp, vp, vp]),
-        "he_rollout_policy": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp]),
-        "he_num_envs": (i64, [vp]),
-        "he_episode_length": (i32, [vp]),
-        "he_num_episodes": (i64, [vp]),
-        "he_get_config": (i32, [vp, ctypes.POINTER(HeConfig)]),
-        "he_state_size": (ctypes.c_size_t, [vp]),
-        "he_get_state": (i32, [vp, vp, ctypes.c_size_t]),
-        "he_set_state": (i32, [vp, vp, ctypes.c_size_t]),
-        "he_pcg64_seed_state": (i32, [u64, ctypes.POINTER(ctypes.c_uint64 * 4)]),
-        "he_host_episode_draws": (i32, [u64, u64, i64, vp]),
-        "he_host_philox": (i32, [u64, u64, u64, ctypes.POINTER(ctypes.c_uint32 * 4)]),
-        "he_host_div_by": (i32, [ctypes.c_void_p, i64, ctypes.c_double, ctypes.c_void_p]),
-        "he_host_div_byf": (i32, [ctypes.c_void_p, i64, ctypes.c_float, ctypes.c_void_p]),
-        "he_host_box_muller": (i32, [ctypes.c_void_p, ctypes.c_void_p, i64, ctypes.c_void_p, ctypes.c_void_p]),
-        "he_time_next_step": (i32, [vp, vp, vp]),
-        "he_sync_market": (i32, [vp, vp]),
-        "he_vecnorm_stats_len": (i64, [i32]),
-        "he_vecnorm_scratch_bytes": (i64, [i64, i32]),
-        "he_vecnorm_init": (i32, [vp, i32, vp]),
-        "he_vecnorm_step": (i32, [ctypes.POINTER(HeVecnormParams), i64] + [vp] * 15 + [vp]),
-        "he_vecnorm_apply": (i32, [ctypes.POINTER(HeVecnormParams), i64] + [vp] * 15 + [vp]),
-        "he_vecnorm_attach": (i32, [vp, ctypes.POINTER(HeVecnormParams), vp, vp, vp]),
-        "he_vecnorm_attach_eval": (i32, [vp, ctypes.POINTER(HeVecnormParams), ctypes.POINTER(HeVecnormOut)]),
-        "he_vecnorm_reset": (i32, [ctypes.POINTER(HeVecnormParams), i64] + [vp] * 5 + [vp]),
-        "he_host_vecnorm_sb3": (i32, [ctypes.POINTER(HeVecnormParams), i64] + [vp] * 9),
-        "he_fixed_european_marks": (i32, [vp, i64, i32, ctypes.c_double, vp, vp, vp, vp]),
-        "he_bs_delta_hedge": (i32, [vp, i64, i32, ctypes.c_double, ctypes.c_double, vp, vp]),
-        "he_count_nonfinite": (i32, [vp, i64, vp, vp]),
-        "he_device_rng": (i32, [u64, vp, vp, i64, vp, vp, vp]),
-        "he_device_math": (i32, [i32, vp, i64, vp, vp]),
-        "he_host_math": (i32, [i32, vp, i64, vp]),
-        "he_host_episode_wrap": (i32, [vp, vp, vp, i64, i32, vp]),
-        "he_episode_summaries": (i32, [vp, vp, vp]),
-        "he_host_alloc": (i32, [ctypes.c_size_t, ctypes.POINTER(vp), ctypes.POINTER(vp)]),
-        "he_host_free": (i32, [vp]),
-        "he_stream_wait": (i32, [vp]),
-        "he_step_signal": (i32, [vp, vp]),
-        "he_signal_seq": (ctypes.c_uint32, [vp]),
-        "he_signal_wait": (i32, [vp, vp, vp]),
-    }
-    ab = path != os.path.join(HERE, "lib", "libhedgeenv.so")  # an A/B build of an older tree
-    for name, (res, args) in sig.items():
-        if ab and not hasattr(lib, name):
-            continue
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = _bind.load(path, SIG, HedgeEnvError, "There is no CPU fallback.",
+                          missing_ok=path != os.path.join(HERE, "lib", "libhedgeenv.so"))
+    return _lib
 
 
 def check(lib, handle, status, what):

@@ -22,7 +22,7 @@ import zipfile
 
 import numpy as np
 
-from . import _lib
+from . import _bind, _lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libhedgeactor.so")
@@ -67,12 +67,6 @@ CRITIC_KEYS = (
 POLICY_KEYS = ACTOR_KEYS + CRITIC_KEYS
 HA_POLICY_ABI_VERSION = 1
 
-EXPORTS = ["ha_version", "ha_last_error", "ha_create", "ha_destroy", "ha_step", "ha_accumulate", "ha_host_step",
-           "ha_policy_last_error", "ha_policy_create", "ha_policy_destroy", "ha_policy_update", "ha_policy_step",
-           "ha_gae", "ha_host_policy_step", "ha_host_gae", "ha_lstm_seq_workspace_bytes", "ha_lstm_seq_forward",
-           "ha_lstm_seq_backward", "ha_host_lstm_seq_forward", "ha_host_lstm_seq_backward",
-           "ha_lstm_seq_weight_grads_workspace_bytes", "ha_lstm_seq_weight_grads", "ha_host_lstm_seq_weight_grads",
-           "ha_policy_refresh", "ha_policy_download", "ha_adam_workspace_bytes", "ha_adam_step", "ha_host_adam_step"]
 POLICY_TENSOR_FLOATS = sum(int(np.prod(shape)) for _, _, shape in POLICY_KEYS)   # HA_POLICY_TENSOR_FLOATS
 assert POLICY_TENSOR_FLOATS == 171461
 
@@ -94,6 +88,41 @@ class HaPolicyWeights(ctypes.Structure):
                [(f, _F) for _, f, _ in POLICY_KEYS]
 
 
+_vp, _i32, _i64, _u64, _f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double
+_W, _PW = ctypes.POINTER(HaWeights), ctypes.POINTER(HaPolicyWeights)
+# every entry point of include/hedge_actor.h: symbol -> (restype, argtypes)
+SIG = {
+    "ha_version": (ctypes.c_char_p, []),
+    "ha_last_error": (ctypes.c_char_p, [_vp]),
+    "ha_create": (_i32, [_W, ctypes.POINTER(_vp)]),
+    "ha_destroy": (_i32, [_vp]),
+    "ha_step": (_i32, [_vp, _i64] + [_vp] * 8),
+    "ha_accumulate": (_i32, [_vp, _i64, _i64] + [_vp] * 10 + [_i64, _vp, _vp]),
+    "ha_host_step": (_i32, [_W, _i64] + [_vp] * 7),
+    "ha_policy_last_error": (ctypes.c_char_p, [_vp]),
+    "ha_policy_create": (_i32, [_PW, ctypes.POINTER(_vp)]),
+    "ha_policy_destroy": (_i32, [_vp]),
+    "ha_policy_update": (_i32, [_vp, _PW]),
+    "ha_policy_step": (_i32, [_vp, _i64, _i64, _u64, _u64, _i32, _i32] + [_vp] * 13),
+    "ha_gae": (_i32, [_i64, _i64, _f64, _f64] + [_vp] * 8),
+    "ha_host_policy_step": (_i32, [_PW, _i64, _i64, _u64, _u64, _i32, _i32] + [_vp] * 12),
+    "ha_host_gae": (_i32, [_i64, _i64, _f64, _f64] + [_vp] * 7),
+    "ha_lstm_seq_workspace_bytes": (ctypes.c_size_t, [_i64]),
+    "ha_lstm_seq_forward": (_i32, [_i64, _i64, _i64] + [_vp] * 5),
+    "ha_lstm_seq_backward": (_i32, [_i64, _i64, _i64] + [_vp] * 4),
+    "ha_host_lstm_seq_forward": (_i32, [_i64, _i64, _i64] + [_vp] * 3),
+    "ha_host_lstm_seq_backward": (_i32, [_i64, _i64, _i64] + [_vp] * 2),
+    "ha_lstm_seq_weight_grads_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64]),
+    "ha_lstm_seq_weight_grads": (_i32, [_i64, _i64, _i64] + [_vp] * 5),
+    "ha_host_lstm_seq_weight_grads": (_i32, [_i64, _i64, _i64] + [_vp] * 3),
+    "ha_policy_refresh": (_i32, [_vp, _PW, _vp]),
+    "ha_policy_download": (_i32, [_vp, _vp, _vp]),
+    "ha_adam_workspace_bytes": (ctypes.c_size_t, [_i64, _vp]),
+    "ha_adam_step": (_i32, [_i64, _vp, _vp, _vp, _vp]),
+    "ha_host_adam_step": (_i32, [_i64, _vp, _vp]),
+}
+EXPORTS = list(SIG)
+
 _lib_ha = None
 _torch = None   # the torch module, from the first device handle on (this module imports without torch)
 
@@ -101,55 +130,9 @@ _torch = None   # the torch module, from the first device handle on (this module
 def load(path=LIB_PATH):
     """Load libhedgeactor (once).  Raises if the in-tree library is missing."""
     global _lib_ha
-    if _lib_ha is not None:
-        return _lib_ha
-    if not os.path.exists(path):
-        raise _lib.HedgeEnvError(f"{path} not found: build it with `python -m cantorrl_amd.build` "
-                                 "(hipcc --offload-arch=gfx950).  There is no torch fallback.")
-    try:
-        import torch  # noqa: F401  (bind to torch's HIP runtime, as _lib.load)
-    except ImportError:
-        pass
-    lib = ctypes.CDLL(path)
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    u64, f64 = ctypes.c_uint64, ctypes.c_double
-    W, PW = ctypes.POINTER(HaWeights), ctypes.POINTER(HaPolicyWeights)
-    sig = {
-        "ha_version": (ctypes.c_char_p, []),
-        "ha_last_error": (ctypes.c_char_p, [vp]),
-        "ha_create": (i32, [W, ctypes.POINTER(vp)]),
-        "ha_destroy": (i32, [vp]),
-        "ha_step": (i32, [vp, i64] + [vp] * 8),
-        "ha_accumulate": (i32, [vp, i64, i64] + [vp] * 10 + [i64, vp, vp]),
-        "ha_host_step": (i32, [W, i64] + [vp] * 7),
-        "ha_policy_last_error": (ctypes.c_char_p, [vp]),
-        "ha_policy_create": (i32, [PW, ctypes.POINTER(vp)]),
-        "ha_policy_destroy": (i32, [vp]),
-        "ha_policy_update": (i32, [vp, PW]),
-        "ha_policy_step": (i32, [vp, i64, i64, u64, u64, i32, i32] + [vp] * 13),
-        "ha_gae": (i32, [i64, i64, f64, f64] + [vp] * 8),
-        "ha_host_policy_step": (i32, [PW, i64, i64, u64, u64, i32, i32] + [vp] * 12),
-        "ha_host_gae": (i32, [i64, i64, f64, f64] + [vp] * 7),
-        "ha_lstm_seq_workspace_bytes": (ctypes.c_size_t, [i64]),
-        "ha_lstm_seq_forward": (i32, [i64, i64, i64] + [vp] * 5),
-        "ha_lstm_seq_backward": (i32, [i64, i64, i64] + [vp] * 4),
-        "ha_host_lstm_seq_forward": (i32, [i64, i64, i64] + [vp] * 3),
-        "ha_host_lstm_seq_backward": (i32, [i64, i64, i64] + [vp] * 2),
-        "ha_lstm_seq_weight_grads_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64]),
-        "ha_lstm_seq_weight_grads": (i32, [i64, i64, i64] + [vp] * 5),
-        "ha_host_lstm_seq_weight_grads": (i32, [i64, i64, i64] + [vp] * 3),
-        "ha_policy_refresh": (i32, [vp, PW, vp]),
-        "ha_policy_download": (i32, [vp, vp, vp]),
-        "ha_adam_workspace_bytes": (ctypes.c_size_t, [i64, vp]),
-        "ha_adam_step": (i32, [i64, vp, vp, vp, vp]),
-        "ha_host_adam_step": (i32, [i64, vp, vp]),
-    }
-    for name, (res, args) in sig.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _lib_ha = lib
-    return lib
+    if _lib_ha is None:
+        _lib_ha = _bind.load(path, SIG, _lib.HedgeEnvError, "There is no torch fallback.")
+    return _lib_ha
 
 
 def _check(lib, status, what, handle=None, last_error="ha_last_error"):
@@ -307,8 +290,7 @@ class _Recurrent:
         return self._h
 
     def _stream(self):
-        from .vec_env import _raw_stream
-        return _raw_stream(self.device.index)
+        return _bind.stream(self.device.index)
 
     def _begin_step(self, obs, episode_start):
         """The head of a device step: the handle, and obs [n,13] f32 and episode_start [n] u8 / bool

@@ -10,12 +10,11 @@ device tensors (NumPy in, NumPy out when return_numpy=True).  The expanding-wind
 realized volatility is a running scan, O(n_steps) per path instead of the
 reference's O(n_steps^2).  No CPU fallback.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
+from ._bind import ptr, stream_of
 
 RISK_FREE_RATE = 0.04
 DT = 1 / 252
@@ -30,15 +29,6 @@ def _paths(paths, device):
     return torch.as_tensor(a, device=device), True
 
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _check(st, what):
-    if st != _lib.HE_OK:
-        raise _lib.HedgeEnvError(f"{what} failed with status {st}")
-
-
 def _out(t, to_numpy):
     return t.cpu().numpy() if to_numpy else t
 
@@ -49,9 +39,8 @@ def fixed_european_marks(paths, r=RISK_FREE_RATE, device="cuda", return_numpy=No
     p, was_np = _paths(paths, device)
     n, c = p.shape
     vols, calls, puts = (torch.empty((n, c), dtype=torch.float64, device=p.device) for _ in range(3))
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    _check(lib.he_fixed_european_marks(ptr(p), n, c, float(r), ptr(vols), ptr(calls), ptr(puts), _stream(p.device)),
-           "he_fixed_european_marks")
+    _lib.check(lib, None, lib.he_fixed_european_marks(ptr(p), n, c, float(r), ptr(vols), ptr(calls), ptr(puts),
+                                                      stream_of(p.device)), "he_fixed_european_marks")
     to_np = was_np if return_numpy is None else return_numpy
     return _out(vols, to_np), _out(calls, to_np), _out(puts, to_np)
 
@@ -72,6 +61,6 @@ def bs_delta_hedge(paths, r=RISK_FREE_RATE, dt=DT, device="cuda", return_numpy=N
     p, was_np = _paths(paths, device)
     n, c = p.shape
     pnl = torch.empty((n, c), dtype=torch.float64, device=p.device)
-    _check(lib.he_bs_delta_hedge(ctypes.c_void_p(p.data_ptr()), n, c, float(r), float(dt),
-                                 ctypes.c_void_p(pnl.data_ptr()), _stream(p.device)), "he_bs_delta_hedge")
+    _lib.check(lib, None, lib.he_bs_delta_hedge(ptr(p), n, c, float(r), float(dt), ptr(pnl), stream_of(p.device)),
+               "he_bs_delta_hedge")
     return _out(pnl, was_np if return_numpy is None else return_numpy)

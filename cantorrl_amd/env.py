@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .vec_env import (HedgingVecEnv, OBS_HIGH, OBS_LOW)
+from .vec_env import HedgingVecEnv, OBS_HIGH, OBS_LOW, set_reference_attrs
 from .spaces import Box
 
 # the info fields HedgingEnv.step reads from the step's block, by dtype (hedging_env_v2.py:268-293)
@@ -66,24 +66,15 @@ class HedgingEnv:
                                    generate=generate, device=device, autoreset=False, return_numpy=False,
                                    info_keys=keys, host_io=True, **kw)
         v = self._venv
+        set_reference_attrs(self, kw)
         self.pnl_penalty_weight = kw["pnl_penalty_weight"]
         self.lambda_cost = kw["lambda_cost"]
         if self._variant == 2:
             self.theta_weight = kw["theta_weight"]
             self.slippage_bps = kw["slippage_bps"]
-        self.loss_type = kw["loss_type"]
-        self.record_metrics = kw["record_metrics"]
         self.initial_cash = kw["initial_cash"]
-        self._max_trade_per_step_internal = kw["max_trade_per_step"]
-        self.max_trade_per_step = kw["max_trade_per_step"]
         self.num_episodes = v.num_episodes
         self.episode_length = v.episode_length
-        self.transaction_cost_per_contract = kw["transaction_cost_per_contract"]
-        self.max_contracts_held = kw["max_contracts_held_per_type"]
-        self.shares_held_fixed = kw["shares_to_hedge"]
-        self.option_contract_multiplier = 100
-        self.risk_free_rate = 0.04
-        self.option_tenor_years = 30 / 252
         self.action_space = Box(low=-1.0, high=1.0, shape=(2,), dtype=np.float32)
         self.observation_space = Box(low=OBS_LOW, high=OBS_HIGH, shape=(13,), dtype=np.float32)
         self.current_episode_idx = -1
@@ -96,23 +87,17 @@ class HedgingEnv:
         # flags and every info field into it, read here through a structured dtype: one launch
         # and one stream wait per step, no DMA.  A reset (rare) writes the device io buffer and
         # comes back as one copy into a pinned mirror of the same layout.
-        self._io_h = torch.zeros(v._io.numel(), dtype=torch.uint8, pin_memory=True)
-        fields = {"names": ["obs", "reward", "terminated"], "formats": [("<f4", (13,)), "<f4", "u1"],
-                  "offsets": [0, 52, 56]}
-        for k, dt, o in v._info_offs:
-            fields["names"].append(k)
-            fields["formats"].append(np.dtype(dict(_lib.INFO_FIELDS)[k]))
-            fields["offsets"].append(v._io_info0 + o)
-        fields["itemsize"] = v._io.numel()
-        rec_dt = np.dtype(fields)
-        self._rec = self._io_h.numpy().view(rec_dt)   # shape (1,): a view, refreshed by each copy
+        L = v._layout
+        self._io_h = torch.zeros(L.total, dtype=torch.uint8, pin_memory=True)
+        self._rec = self._io_h.numpy().view(L.record_dtype())   # shape (1,): a view, refreshed by each copy
         self._ev = torch.cuda.Event()
         # a step reads the mapped block by three gathers (f64, i32, f32 fields), whose numpy
-        # scalars fill the info dict: ~45 structured-field reads cost more than the step itself
-        offs = {k: v._io_info0 + o for k, dt, o in v._info_offs}
-        self._g8 = np.array([offs[k] // 8 for k in _STEP_F8], np.intp)
-        self._g4i = np.array([offs[k] // 4 for k in _STEP_I4], np.intp)
-        self._g4f = np.array([offs[k] // 4 for k in _STEP_F4], np.intp)
+        # scalars fill the info dict: ~45 structured-field reads cost more than the step itself.
+        # The block stays where it is, so its views are made once.
+        self._g8, self._g4i, self._g4f = (L.gather_index(keys) for keys in (_STEP_F8, _STEP_I4, _STEP_F4))
+        io = v._hio.io
+        self._io_f8, self._io_i4, self._io_f4 = io.view(np.float64), io.view(np.int32), io.view(np.float32)
+        self._io_obs, self._io_term = io[:L.reward].view(np.float32), io[L.terminated:L.truncated]
 
     # ------------------------------------------------------------------ helpers
     def _fetch(self):
@@ -171,13 +156,13 @@ class HedgingEnv:
         a = np.asarray(action, dtype=np.float32).reshape(2)
         v = self._venv
         prev_S, prev_v = self.current_stock_price, self.current_volatility
-        io = v.step_host(a).io
-        o = io[:52].view(np.float32).copy()
-        terminated = bool(io[56])
+        v.step_host(a)
+        o = self._io_obs.copy()
+        terminated = bool(self._io_term[0])
         # numpy scalars of the reference's dtypes: f64 P&L fields, int64 positions, f32 market
-        pnl, ps, rab, tc, com, slip, rpc, tcp, thp, rew, pv, cash = io.view(np.float64)[self._g8]
-        cc, pc, rqc, rqp, dc, dp, t = io.view(np.int32)[self._g4i].astype(np.int64)
-        sfc, sfp, S, vv, C, P = io.view(np.float32)[self._g4f]
+        pnl, ps, rab, tc, com, slip, rpc, tcp, thp, rew, pv, cash = self._io_f8[self._g8]
+        cc, pc, rqc, rqp, dc, dp, t = self._io_i4[self._g4i].astype(np.int64)
+        sfc, sfp, S, vv, C, P = self._io_f4[self._g4f]
         self.current_stock_price, self.current_volatility = S, vv
         self.current_call_price, self.current_put_price = C, P
         self.current_step = int(t)

@@ -21,6 +21,9 @@ import os
 
 import numpy as np
 
+from . import _bind
+from ._bind import ptr as _ptr, stream_of as _stream
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 # CANTORRL_RBERGOMI_LIB: an alternative build (e.g. the host-ASan build of tools/asan/run.sh)
 LIB_PATH = os.environ.get("CANTORRL_RBERGOMI_LIB") or os.path.join(HERE, "lib", "librbergomi.so")
@@ -77,9 +80,24 @@ class RbConfig(ctypes.Structure):
     ]
 
 
-EXPORTS = ["rb_version", "rb_last_error", "rb_config_init", "rb_estimate_base_params", "rb_estimate_parts",
-           "rb_sample_params", "rb_simulate_paths", "rb_price_options", "rb_price_atm_marks", "rb_generate",
-           "rb_host_normals", "rb_device_mc_box_muller"]
+_vp, _i32, _i64, _u32, _u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64
+_cfgp, _basep = ctypes.POINTER(RbConfig), ctypes.POINTER(RbBaseParams)
+# every entry point of include/rbergomi.h: symbol -> (restype, argtypes)
+SIG = {
+    "rb_version": (ctypes.c_char_p, []),
+    "rb_last_error": (ctypes.c_char_p, []),
+    "rb_config_init": (_i32, [_cfgp, _i32]),
+    "rb_estimate_base_params": (_i32, [_vp, _i64, ctypes.c_double, _basep]),
+    "rb_estimate_parts": (_i32, [_vp, _i64, ctypes.c_double, _vp]),
+    "rb_sample_params": (_i32, [_cfgp, _basep, _vp, _vp, _vp]),
+    "rb_simulate_paths": (_i32, [_cfgp, _vp, _vp, _vp, _vp, _vp]),
+    "rb_price_options": (_i32, [_cfgp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rb_price_atm_marks": (_i32, [_cfgp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rb_generate": (_i32, [_cfgp, _basep, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rb_host_normals": (_i32, [_u64, _i32, _u32, _u64, _u32, _i64, _vp]),
+    "rb_device_mc_box_muller": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
+}
+EXPORTS = list(SIG)
 
 _lib = None
 
@@ -87,37 +105,9 @@ _lib = None
 def load(path=LIB_PATH):
     """Load librbergomi (once).  Raises if the in-tree library is missing."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(path):
-        raise RbergomiError(f"{path} not found: build it with `python -m cantorrl_amd.build` "
-                            "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
-    try:
-        import torch  # noqa: F401  (bind to torch's HIP runtime first, as _lib.py does)
-    except ImportError:
-        pass
-    lib = ctypes.CDLL(path)
-    vp, i32, i64, u32, u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64
-    cfgp, basep = ctypes.POINTER(RbConfig), ctypes.POINTER(RbBaseParams)
-    sig = {
-        "rb_version": (ctypes.c_char_p, []),
-        "rb_last_error": (ctypes.c_char_p, []),
-        "rb_config_init": (i32, [cfgp, i32]),
-        "rb_estimate_base_params": (i32, [vp, i64, ctypes.c_double, basep]),
-        "rb_estimate_parts": (i32, [vp, i64, ctypes.c_double, vp]),
-        "rb_sample_params": (i32, [cfgp, basep, vp, vp, vp]),
-        "rb_simulate_paths": (i32, [cfgp, vp, vp, vp, vp, vp]),
-        "rb_price_options": (i32, [cfgp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "rb_price_atm_marks": (i32, [cfgp, vp, vp, vp, vp, vp, vp]),
-        "rb_generate": (i32, [cfgp, basep, vp, vp, vp, vp, vp, vp]),
-        "rb_host_normals": (i32, [u64, i32, u32, u64, u32, i64, vp]),
-        "rb_device_mc_box_muller": (i32, [vp, vp, i64, vp, vp, vp]),
-    }
-    for name, (res, args) in sig.items():
-        f = getattr(lib, name)
-        f.restype, f.argtypes = res, args
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = _bind.load(path, SIG, RbergomiError, "There is no CPU fallback.")
+    return _lib
 
 
 def _check(status):
@@ -159,20 +149,11 @@ def _torch():
     return torch
 
 
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def _dev_f64(x, device):
     torch = _torch()
     if isinstance(x, torch.Tensor):
         return x.to(device=device, dtype=torch.float64).contiguous()
     return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device=device)
-
-
-def _stream(device):
-    torch = _torch()
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def sample_params(cfg, base, device="cuda", unit_normals=None):

@@ -32,6 +32,7 @@ from torch.autograd.function import once_differentiable
 
 from .agent import (ACT_DIM, HIDDEN, MLP, OBS_DIM, POLICY_KEYS, STATE_NAMES, _check, _normalization, _read_sb3_zip,
                     load)
+from ._bind import stream_of as _stream   # the current stream of a torch.device (raw handle)
 
 _VP = ctypes.c_void_p
 NET_INPUTS = ("h0", "c0", "w_ih", "w_hh", "b_ih", "b_hh")   # lstm_sequence's per-network arguments
@@ -75,11 +76,6 @@ def _starts(es, L, B, device):
         raise ValueError(f"episode_starts must be a uint8 / bool [{L}, {B}] tensor on {device}")
     es = es.contiguous()
     return es.clone() if es.data_ptr() % 16 else es
-
-
-def _stream(device):
-    from .vec_env import _raw_stream
-    return _raw_stream(device.index if device.index is not None else torch.cuda.current_device())
 
 
 @functools.lru_cache(maxsize=16)

@@ -17,7 +17,9 @@ import weakref
 import numpy as np
 import torch
 
-from . import _lib
+from . import _bind, _lib
+from ._bind import ptr as _ptr
+from ._layout import IoLayout
 from .spaces import Box
 
 try:   # the C rows of an info view (csrc/info_rows.c, built with the HIP libraries)
@@ -47,17 +49,16 @@ MONITOR_KEYWORDS = ("per_share_step_pnl", "raw_pnl_deviation_abs", "transaction_
 # 53 against 67 us at 8,192 envs, 105 against 79 us at 16,384 (the kernel's PCIe writes).
 HOST_IO_MAX_ENVS = 8192
 
-_TORCH_DT = {"f8": torch.float64, "f4": torch.float32, "i4": torch.int32}
-_NP_DT = {torch.float64: np.float64, torch.float32: np.float32, torch.int32: np.int32}
+_TORCH_DT = {np.dtype(np.float64): torch.float64, np.dtype(np.float32): torch.float32,
+             np.dtype(np.int32): torch.int32}
 _ROW_KIND = {np.dtype(np.float64): "d", np.dtype(np.float32): "f", np.dtype(np.int32): "i"}
-# the current stream's raw handle (torch's own accessor; current_stream().cuda_stream builds a
-# Stream object per call, a few us of every eager step)
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or \
-    (lambda idx: torch.cuda.current_stream(idx).cuda_stream)
-
-
-def _align(x, a):
-    return -(-x // a) * a
+# he_config fields that take an env keyword / a generate entry of the same name: (field, cast)
+_CFG_ENV = tuple((k, float) for k in ("transaction_cost_per_contract", "lambda_cost", "pnl_penalty_weight",
+                                      "theta_weight", "slippage_bps", "initial_cash")) + \
+    tuple((k, int) for k in ("shares_to_hedge", "max_contracts_held_per_type", "max_trade_per_step")) + \
+    (("record_metrics", bool),)
+_CFG_GEN = (("episode_length", int),) + tuple((k, float) for k in (
+    "s0", "variance", "mu", "dt", "heston_kappa", "heston_theta", "heston_xi", "heston_rho"))
 
 
 def load_npz_tables(data_file_path):
@@ -78,6 +79,20 @@ def check_table_shapes(S, v, C, P):
     if not (S.ndim == 2 and S.shape == v.shape and S.shape[0] == C.shape[0] == P.shape[0]
             and S.shape[1] == C.shape[1] + 1 == P.shape[1] + 1):
         raise ValueError("Data shapes are inconsistent.")
+
+
+def set_reference_attrs(env, kw):
+    """The reference env's attribute names (hedging_env_v2.py:53-58) + the documented alias
+    max_trade_per_step, on a HedgingVecEnv or a HedgingEnv, from the ctor keywords."""
+    env.transaction_cost_per_contract = kw["transaction_cost_per_contract"]
+    env.max_contracts_held = kw["max_contracts_held_per_type"]
+    env.shares_held_fixed = kw["shares_to_hedge"]
+    env.option_contract_multiplier = 100
+    env.risk_free_rate = 0.04
+    env.option_tenor_years = 30 / 252
+    env.max_trade_per_step = env._max_trade_per_step_internal = kw["max_trade_per_step"]
+    env.loss_type = kw["loss_type"]
+    env.record_metrics = kw["record_metrics"]
 
 
 class HedgingVecEnv:
@@ -130,27 +145,12 @@ class HedgingVecEnv:
         cfg.loss_type = _lib.loss_code(kw["loss_type"])
         cfg.n_envs = self.num_envs
         cfg.global_env_offset = int(global_env_offset)
-        cfg.transaction_cost_per_contract = float(kw["transaction_cost_per_contract"])
-        cfg.lambda_cost = float(kw["lambda_cost"])
-        cfg.pnl_penalty_weight = float(kw["pnl_penalty_weight"])
-        cfg.theta_weight = float(kw.get("theta_weight", 0.0))
-        cfg.slippage_bps = float(kw.get("slippage_bps", 0.0))
-        cfg.initial_cash = float(kw["initial_cash"])
-        cfg.shares_to_hedge = int(kw["shares_to_hedge"])
-        cfg.max_contracts_held_per_type = int(kw["max_contracts_held_per_type"])
-        cfg.max_trade_per_step = int(kw["max_trade_per_step"])
-        cfg.record_metrics = 1 if kw["record_metrics"] else 0
+        for f, cast in _CFG_ENV:
+            setattr(cfg, f, cast(kw.get(f, 0)))   # variant 1 has no theta_weight / slippage_bps: 0
+        for f, cast in _CFG_GEN:
+            setattr(cfg, f, cast(gen[f]))
         cfg.autoreset = 1 if autoreset else 0
         cfg.device = dev_index
-        cfg.episode_length = int(gen["episode_length"])
-        cfg.s0 = float(gen["s0"])
-        cfg.variance = float(gen["variance"])
-        cfg.mu = float(gen["mu"])
-        cfg.dt = float(gen["dt"])
-        cfg.heston_kappa = float(gen["heston_kappa"])
-        cfg.heston_theta = float(gen["heston_theta"])
-        cfg.heston_xi = float(gen["heston_xi"])
-        cfg.heston_rho = float(gen["heston_rho"])
         cfg.market_block = int(market_block)
         mark = gen["mark"]
         if mark not in _lib.MARKS:
@@ -210,40 +210,21 @@ class HedgingVecEnv:
         if self.monitor_keywords is not None and "reward_step" not in layout_keys:
             layout_keys = layout_keys + ("reward_step",)
         self._row_keys = self.info_keys
-        self._info_t = {}
-        self._info = _lib.HeInfo()
-        known = dict(_lib.INFO_FIELDS)
-        # ONE device buffer holds everything a host caller reads after a step:
-        #   [obs f32 N x 13 | reward f32 N | terminated u8 N | truncated u8 N | info fields]
-        # with every info field 256-B aligned.  step_wait copies the obs / reward / terminated
-        # prefix to the host as one DMA and HedgingEnv.step the whole buffer (~7 KB at N = 1);
-        # freezing an InfoView is one device copy of the info part, not one per key.
-        o_rew, o_term = 52 * n, 56 * n
-        o_trunc, end = o_term + n, o_term + 2 * n
-        self._io_step_bytes = o_trunc            # obs + reward + terminated
-        info0 = _align(end, 256)
-        offs, tot = [], 0
-        for k in layout_keys:
-            if k not in known:
-                raise KeyError(f"unknown info key {k!r}")
-            dt = _TORCH_DT[known[k]]
-            offs.append((k, dt, tot))
-            tot += _align(n * torch.empty((), dtype=dt).element_size(), 256)
-        self._io = torch.zeros(info0 + tot, dtype=torch.uint8, device=dev)
-        self._obs = self._io[:o_rew].view(torch.float32).view(n, 13)
-        self._rew = self._io[o_rew:o_term].view(torch.float32)
-        self._term = self._io[o_term:o_trunc]
-        self._trunc = self._io[o_trunc:end]
-        self._io_info0 = info0
-        self._info_flat = self._io[info0:]
-        for k, dt, o in offs:
-            t = self._info_flat[o:o + n * torch.empty((), dtype=dt).element_size()].view(dt)
-            self._info_t[k] = t
-            setattr(self._info, k, t.data_ptr())
-        self._info_offs = offs
+        # ONE device buffer holds everything a host caller reads after a step (_layout.IoLayout)
+        L = self._layout = IoLayout(n, layout_keys)
+        io = self._io = torch.zeros(L.total, dtype=torch.uint8, device=dev)
+        self._obs = io[:L.reward].view(torch.float32).view(n, 13)
+        self._rew = io[L.reward:L.terminated].view(torch.float32)
+        self._term = io[L.terminated:L.truncated]
+        self._trunc = io[L.truncated:L.truncated + n]
+        self._io_step = io[:L.truncated]   # what step_wait copies: obs, reward, terminated
+        self._info_flat = io[L.info0:]
+        self._info_t = {k: io[o:o + b].view(_TORCH_DT[dt]) for k, (dt, o, b) in L.fields.items()}
+        self._info = _lib.HeInfo(**{k: t.data_ptr() for k, t in self._info_t.items()})
         self._ev = torch.cuda.Event()   # the one host wait of a host pull (_pull)
+        self._info_ref = _lib.ctypes.byref(self._info) if self._info_t else None
         self._step_args = (self._obs.data_ptr(), self._rew.data_ptr(), self._term.data_ptr(), self._trunc.data_ptr(),
-                           self._tobs.data_ptr(), _lib.ctypes.byref(self._info) if self._info_t else None)
+                           self._tobs.data_ptr(), self._info_ref)
         # InfoView snapshots (see InfoView): freeze_infos=False skips them (a view read after
         # a later step then shows that step's values)
         self.freeze_infos = bool(freeze_infos)
@@ -278,7 +259,7 @@ class HedgingVecEnv:
         if self.return_numpy:
             # the host path's pinned blocks (step outputs, actions, the episode-end pull), made
             # now: a first hipHostMalloc costs milliseconds, inside a step it would be that step's
-            self._warm_pinned([self._io_step_bytes] * 3 + [8 * n] * 2 + [52 * n, self._info_flat.numel(), 8 * n])
+            self._warm_pinned([L.truncated] * 3 + [8 * n] * 2 + [4 * self._tobs.numel(), L.total - L.info0, 8 * n])
         if self.monitor_keywords is not None:
             # the Monitor sums' torch kernels, loaded now (a first launch loads the code object:
             # tens of ms, which the first episode end would otherwise pay)
@@ -287,26 +268,13 @@ class HedgingVecEnv:
             self._ep_ret.zero_()
         self.action_space = Box(-1.0, 1.0, (2,), np.float32)
         self.observation_space = Box(OBS_LOW, OBS_HIGH, (13,), np.float32)
-        # reference attribute names (hedging_env_v2.py:53-58) + the documented alias
-        self.transaction_cost_per_contract = kw["transaction_cost_per_contract"]
-        self.max_contracts_held = kw["max_contracts_held_per_type"]
-        self.shares_held_fixed = kw["shares_to_hedge"]
-        self.option_contract_multiplier = 100
-        self.risk_free_rate = 0.04
-        self.option_tenor_years = 30 / 252
-        self.max_trade_per_step = kw["max_trade_per_step"]
-        self._max_trade_per_step_internal = kw["max_trade_per_step"]
-        self.loss_type = kw["loss_type"]
-        self.record_metrics = kw["record_metrics"]
+        set_reference_attrs(self, kw)
 
     # ------------------------------------------------------------------ plumbing
     @property
     def stream(self):
         """The caller's current stream on the env device (raw handle)."""
-        return _raw_stream(self._dev_index)
-
-    def _ptr(self, t):
-        return t.data_ptr() if t is not None else None
+        return _bind.stream(self._dev_index)
 
     def _pull(self, srcs):
         """Device tensors -> numpy arrays in pinned host memory: one async copy each on the
@@ -339,11 +307,6 @@ class HedgingVecEnv:
             a = stage
         self._act.copy_(a, non_blocking=True)
         return self._act
-
-    def _split_info(self, flat):
-        """Host bytes of the info part of the io buffer -> {key: numpy array}."""
-        n = self.num_envs
-        return {k: flat[o:o + n * np.dtype(_NP_DT[dt]).itemsize].view(_NP_DT[dt]) for k, dt, o in self._info_offs}
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -413,29 +376,20 @@ class HedgingVecEnv:
         if self._pending_seeds is not None:
             self.seed_envs(self._pending_seeds)
             self._pending_seeds = None
-        info = _lib.ctypes.byref(self._info) if self._info_t else None
-        if episode_idx is not None:
-            eps = np.ascontiguousarray(np.asarray(episode_idx, dtype=np.int64).reshape(-1))
-            ids = None
-            if env_ids is not None:
-                ids = torch.as_tensor(env_ids, dtype=torch.int64, device=self.device).reshape(-1)
-                if ids.numel() != eps.size:
-                    raise ValueError(f"{eps.size} episode indices for {ids.numel()} envs")
-            elif eps.size != self.num_envs:
-                raise ValueError(f"{eps.size} episode indices for {self.num_envs} envs")
-            st = self.lib.he_reset_episodes(self._h, None if ids is None else ids.data_ptr(),
-                                            eps.ctypes.data, eps.size, self._obs.data_ptr(), info, self.stream)
-            _lib.check(self.lib, self._h, st, "he_reset_episodes")
-            if env_ids is None:
-                self._monitor_reset()
-            return self._obs
-        if env_ids is None:
-            st = self.lib.he_reset(self._h, None, self.num_envs, self._obs.data_ptr(), info, self.stream)
+        info = self._info_ref
+        ids = None if env_ids is None else torch.as_tensor(env_ids, dtype=torch.int64, device=self.device).reshape(-1)
+        count = self.num_envs if ids is None else ids.numel()
+        if episode_idx is None:
+            what = "he_reset"
+            st = self.lib.he_reset(self._h, _ptr(ids), count, self._obs.data_ptr(), info, self.stream)
         else:
-            ids = torch.as_tensor(env_ids, dtype=torch.int64, device=self.device)
-            st = self.lib.he_reset(self._h, ids.data_ptr(), ids.numel(), self._obs.data_ptr(), info,
-                                   self.stream)
-        _lib.check(self.lib, self._h, st, "he_reset")
+            what = "he_reset_episodes"
+            eps = np.ascontiguousarray(np.asarray(episode_idx, dtype=np.int64).reshape(-1))
+            if eps.size != count:
+                raise ValueError(f"{eps.size} episode indices for {count} envs")
+            st = self.lib.he_reset_episodes(self._h, _ptr(ids), eps.ctypes.data, eps.size, self._obs.data_ptr(),
+                                            info, self.stream)
+        _lib.check(self.lib, self._h, st, what)
         if env_ids is None:
             self._monitor_reset()
         return self._obs
@@ -460,7 +414,7 @@ class HedgingVecEnv:
         # the output pointers are fixed allocations: marshalled once (_step_args)
         o, r, t, tr, tob, inf = self._step_args
         st = self.lib.he_step(self._h, act.data_ptr(), o, r, t, tr, tob if terminal_obs else None,
-                              inf if info else None, _raw_stream(self._dev_index))
+                              inf if info else None, _bind.stream(self._dev_index))
         _lib.check(self.lib, self._h, st, "he_step")
         if self.check_finite:
             for t in (self._obs, self._rew):
@@ -488,11 +442,7 @@ class HedgingVecEnv:
         if self.monitor_keywords is not None:
             self._ep_ret.add_(self._rew64)   # Monitor.step: the env's f64 reward
         # obs, reward and terminated are adjacent in the io buffer: one DMA, one wait
-        n = self.num_envs
-        h = self._pull([self._io[:self._io_step_bytes]])[0]
-        obs_h = h[:52 * n].view(np.float32).reshape(n, 13)
-        rew_h = h[52 * n:56 * n].view(np.float32)
-        done_h = h[56 * n:57 * n].view(np.bool_)   # the kernels store 0 / 1
+        obs_h, rew_h, done_h = self._layout.unpack(self._pull([self._io_step])[0])
         infos = InfoView(self, done_h)
         if done_h.any():
             infos._materialize_done(done_h)
@@ -511,7 +461,7 @@ class HedgingVecEnv:
         np.copyto(z.act, np.asarray(actions, dtype=np.float32).reshape(self.num_envs, 2))
         self._retire_view()
         lib, h = self.lib, self._h
-        stream = _raw_stream(self._dev_index)
+        stream = _bind.stream(self._dev_index)
         if not self.check_finite:
             # the step kernel raises the block's flag word after its outputs (he_step_signal):
             # the host reads it instead of waiting for the runtime's completion (~5 us less)
@@ -520,8 +470,8 @@ class HedgingVecEnv:
             _lib.check(lib, h, lib.he_signal_wait(h, z.h_flag, stream), "he_signal_wait")
             return z
         _lib.check(lib, h, lib.he_step(h, *z.step_args, stream), "he_step")
-        for p, c in ((z.d_obs, 13 * self.num_envs), (z.d_rew, self.num_envs)):
-            _lib.check(lib, h, lib.he_count_nonfinite(p, c, self._nonfinite.data_ptr(), self.stream),
+        for p, c in ((z.step_args[1], self._obs.numel()), (z.step_args[2], self.num_envs)):   # obs, reward
+            _lib.check(lib, h, lib.he_count_nonfinite(p, c, self._nonfinite.data_ptr(), stream),
                        "he_count_nonfinite")
         _lib.check(lib, h, lib.he_stream_wait(stream), "he_stream_wait")
         return z
@@ -532,24 +482,17 @@ class HedgingVecEnv:
         its host columns, and the Monitor sums are host f64 additions of the env's rewards."""
         z = self.step_host(actions)
         self._steps += 1
-        n = self.num_envs
+        L = self._layout
         h = z.io.copy()
-        obs_h = h[:52 * n].view(np.float32).reshape(n, 13)
-        rew_h = h[52 * n:56 * n].view(np.float32)
-        done_h = h[56 * n:57 * n].view(np.bool_)   # the kernels store 0 / 1
+        obs_h, rew_h, done_h = L.unpack(h)
         infos = InfoView(self, done_h)
-        host = infos._host = self._split_info(h[self._io_info0:])
+        host = infos._host = L.split_info(h[L.info0:])
         mon = self.monitor_keywords is not None
         if mon:
             self._ep_ret_h += host["reward_step"]   # Monitor.step: the env's f64 reward
         if done_h.any():
-            er = el = None
-            if mon:
-                er = self._ep_ret_h.copy()
-                el = self._steps - self._ep_start
-                self._ep_ret_h[done_h] = 0.0
-                self._ep_start[done_h] = self._steps
-            infos._ends = (z.tobs.copy(), er, el, round(time.time() - self._t_start, 6), mon)
+            infos._ends = _end_episodes(self, done_h, z.tobs.copy(), self._ep_ret_h if mon else None, None,
+                                        self._t_start, mon)
         return obs_h, rew_h, done_h, infos
 
     def sync_market(self):
@@ -570,8 +513,8 @@ class HedgingVecEnv:
         if terminated is None:
             terminated = torch.empty((K, n), dtype=torch.uint8, device=dev)
         actions = actions.to(device=dev, dtype=torch.float32).contiguous()
-        st = self.lib.he_rollout(self._h, K, actions.data_ptr(), self._ptr(obs), self._ptr(reward),
-                                 self._ptr(terminated), self.stream)
+        st = self.lib.he_rollout(self._h, K, actions.data_ptr(), _ptr(obs), _ptr(reward),
+                                 _ptr(terminated), self.stream)
         _lib.check(self.lib, self._h, st, "he_rollout")
         return obs, reward, terminated
 
@@ -595,30 +538,35 @@ class HedgingVecEnv:
         pol = _lib.POLICIES[policy] if isinstance(policy, str) else int(policy)
         K = int(k_steps)
         cap = 0 if records is None else int(records.shape[0])
-        st = self.lib.he_rollout_policy(self._h, K, pol, self._ptr(actions_out), self._ptr(obs), self._ptr(reward),
-                                        self._ptr(terminated), self._ptr(records), cap, self._ptr(record_count),
+        st = self.lib.he_rollout_policy(self._h, K, pol, _ptr(actions_out), _ptr(obs), _ptr(reward),
+                                        _ptr(terminated), _ptr(records), cap, _ptr(record_count),
                                         self.stream)
         _lib.check(self.lib, self._h, st, "he_rollout_policy")
+
+    def _collect_records(self, run_chunk, num_episodes, chunk, max_steps):
+        """run_chunk(chunk, records=, record_count=) -- `chunk` steps of every env, finished episodes
+        appended -- until num_episodes episodes finished (or max_steps steps ran) -> at most
+        num_episodes EPISODE_RECORD rows as a numpy structured array."""
+        cap = int(num_episodes) + self.num_envs
+        recs = torch.zeros((cap, _lib.EPISODE_RECORD.itemsize), dtype=torch.uint8, device=self.device)
+        cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
+        steps = 0
+        limit = max_steps if max_steps is not None else (num_episodes // self.num_envs + 2) * (self.episode_length + 1)
+        while True:
+            run_chunk(chunk, records=recs, record_count=cnt)
+            steps += chunk
+            if int(cnt.item()) >= num_episodes or steps >= limit:
+                break
+        n = min(int(cnt.item()), cap)
+        out = recs[:n].cpu().numpy().view(_lib.EPISODE_RECORD).reshape(n)
+        return out[:num_episodes]
 
     def evaluate_policy(self, policy, num_episodes, chunk=64, max_steps=None):
         """Run `policy` until `num_episodes` episodes finished (all envs stepping) and
         return the per-episode records as a numpy structured array (he_episode_record):
         the device-side evaluate_baseline_policy (baselines.py:32-72)."""
-        dev = self.device
-        cap = int(num_episodes) + self.num_envs
-        recs = torch.zeros((cap, _lib.EPISODE_RECORD.itemsize), dtype=torch.uint8, device=dev)
-        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-        steps = 0
-        limit = max_steps if max_steps is not None else (num_episodes // self.num_envs + 2) * (self.episode_length + 1)
-        while True:
-            self.rollout_policy(chunk, policy, records=recs, record_count=cnt)
-            steps += chunk
-            done = int(cnt.item())
-            if done >= num_episodes or steps >= limit:
-                break
-        n = min(int(cnt.item()), cap)
-        out = recs[:n].cpu().numpy().view(_lib.EPISODE_RECORD).reshape(n)
-        return out[:num_episodes]
+        return self._collect_records(lambda k, **out: self.rollout_policy(k, policy, **out),
+                                     num_episodes, chunk, max_steps)
 
     def _actor_info_check(self):
         from .agent import RECORD_INFO_KEYS
@@ -670,22 +618,10 @@ class HedgingVecEnv:
         and return exactly that many EPISODE_RECORD rows: run_evaluation's loop
         (train_ppo_v2.py:415-576) on the device; evaluation.py turns the rows into its
         mean / std / CVaR95."""
-        dev = self.device
-        cap = int(num_episodes) + self.num_envs
-        recs = torch.zeros((cap, _lib.EPISODE_RECORD.itemsize), dtype=torch.uint8, device=dev)
-        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
         self._actor_info_check()
         self.reset_tensors()
-        steps = 0
-        limit = max_steps if max_steps is not None else (num_episodes // self.num_envs + 2) * (self.episode_length + 1)
-        while True:
-            self.rollout_actor(actor, chunk, records=recs, record_count=cnt)
-            steps += chunk
-            if int(cnt.item()) >= num_episodes or steps >= limit:
-                break
-        n = min(int(cnt.item()), cap)
-        out = recs[:n].cpu().numpy().view(_lib.EPISODE_RECORD).reshape(n)
-        return out[:num_episodes]
+        return self._collect_records(lambda k, **out: self.rollout_actor(actor, k, **out),
+                                     num_episodes, chunk, max_steps)
 
     # ------------------------------------------------------------------ attrs
     def _indices(self, indices):
@@ -727,35 +663,26 @@ class HedgingVecEnv:
 
 
 class _HostIo:
-    """The host-mapped block of the small-N host path (he_host_alloc): the env's io layout
-    [obs | reward | terminated | truncated | info fields] (as the device io buffer), then the
-    actions [N, 2], the terminal obs [N, 13] and the step's completion flag (one u32), each 256-B
-    aligned.  The step kernel reads the actions and writes everything else in place."""
+    """The host-mapped block of the small-N host path (he_host_alloc): the env's io layout (as
+    the device io buffer), then the actions, the terminal obs and the step's completion flag
+    (_layout.IoLayout).  The step kernel reads the actions and writes everything else in place."""
 
     def __init__(self, venv):
-        lib, n = venv.lib, venv.num_envs
+        lib, n, L = venv.lib, venv.num_envs, venv._layout
         c = _lib.ctypes
         self.lib = lib
-        io_b = venv._io.numel()
-        a_off = _align(io_b, 256)
-        t_off = _align(a_off + 8 * n, 256)
-        f_off = _align(t_off + 52 * n, 256)   # the step's completion flag (he_step_signal)
-        total = f_off + 4
         hp, dp = c.c_void_p(), c.c_void_p()
-        _lib.check(lib, None, lib.he_host_alloc(total, c.byref(hp), c.byref(dp)), "he_host_alloc")
+        _lib.check(lib, None, lib.he_host_alloc(L.host_total, c.byref(hp), c.byref(dp)), "he_host_alloc")
         self.host = hp.value
-        base = np.frombuffer((c.c_uint8 * total).from_address(hp.value), np.uint8)
+        base = np.frombuffer((c.c_uint8 * L.host_total).from_address(hp.value), np.uint8)
         d = dp.value
-        self.io = base[:io_b]
-        self.act = base[a_off:a_off + 8 * n].view(np.float32).reshape(n, 2)
-        self.tobs = base[t_off:t_off + 52 * n].view(np.float32).reshape(n, 13)
-        self.d_obs, self.d_rew = d, d + 52 * n
-        self.d_flag, self.h_flag = d + f_off, hp.value + f_off
-        self.info = _lib.HeInfo()
-        for k, dt, o in venv._info_offs:
-            setattr(self.info, k, d + venv._io_info0 + o)
-        self.step_args = (d + a_off, d, d + 52 * n, d + 56 * n, d + 57 * n, d + t_off,
-                          c.byref(self.info) if venv._info_offs else None)
+        self.io = base[:L.total]
+        self.act = base[L.actions:L.terminal_obs].view(np.float32)[:n * 2].reshape(n, 2)
+        self.tobs = base[L.terminal_obs:L.flag].view(np.float32)[:n * 13].reshape(n, 13)
+        self.d_flag, self.h_flag = d + L.flag, hp.value + L.flag
+        self.info = _lib.HeInfo(**{k: d + o for k, (_, o, _) in L.fields.items()})
+        self.step_args = (d + L.actions, d, d + L.reward, d + L.terminated, d + L.truncated, d + L.terminal_obs,
+                          c.byref(self.info) if L.fields else None)
 
     def free(self):
         if self.host:
@@ -807,9 +734,19 @@ class InfoView(_info_rows.Rows):
             if pulled is None:
                 src = self._snap if self._snap is not None else v._info_flat
                 pulled = v._pull([src])[0]
-            self._host = v._split_info(pulled)
+            self._host = v._layout.split_info(pulled)
             self._snap = None
         return self._host
+
+    def _pull_done(self, srcs):
+        """One pull of the device tensors `srcs` and, unless the view has them already, of the
+        info fields (live or frozen) -> the host arrays of `srcs`."""
+        v = self._v
+        if self._host is not None:
+            return v._pull(srcs)
+        got = v._pull(srcs + [self._snap if self._snap is not None else v._info_flat])
+        self._host_info(got.pop())
+        return got
 
     def _load(self):
         """First row access (info_rows.c): attach the host columns to the C rows."""
@@ -834,20 +771,25 @@ class InfoView(_info_rows.Rows):
         the rows' extra items are made when they are read."""
         v = self._v
         mon = v.monitor_keywords is not None
-        srcs = [v._tobs]
-        if self._host is None:
-            srcs.append(self._snap if self._snap is not None else v._info_flat)
-        if mon:
-            srcs.append(v._ep_ret)
-        got = v._pull(srcs)
-        self._host_info(got[1] if self._host is None else None)
-        er = el = None
-        if mon:
-            er = got[-1]
-            el = v._steps - v._ep_start   # a new array: _ep_start moves on below
-            v._ep_ret.masked_fill_(v._term.bool(), 0.0)   # the new episodes start at 0
-            v._ep_start[np.nonzero(done)[0]] = v._steps
-        self._ends = (got[0], er, el, round(time.time() - v._t_start, 6), mon)
+        got = self._pull_done([v._tobs, v._ep_ret] if mon else [v._tobs])
+        self._ends = _end_episodes(v, done, got[0], got[1] if mon else None, None, v._t_start, mon)
+
+
+def _end_episodes(v, done, tobs, ep_ret, ep_len, t_start, mon):
+    """The done rows' host data of a step (InfoView._ends) from the pulled arrays: the terminal obs
+    and, with Monitor (mon), the episode returns and lengths.  ep_len None: Monitor is the env's
+    own -- the lengths come from its step count, and the done envs' episodes begin anew here (their
+    start step, and their sums zeroed: ep_ret is either the host path's live sums or a pull of the
+    device sums)."""
+    if mon and ep_len is None:
+        ep_len = v._steps - v._ep_start   # a new array: _ep_start moves on below
+        v._ep_start[done] = v._steps
+        if ep_ret is v._ep_ret_h:
+            ep_ret = ep_ret.copy()
+            v._ep_ret_h[done] = 0.0
+        else:
+            v._ep_ret.masked_fill_(v._term.bool(), 0.0)
+    return (tobs, ep_ret, ep_len, round(time.time() - t_start, 6), mon)
 
 
 def _episode_ends(ends, host, monitor_keywords):

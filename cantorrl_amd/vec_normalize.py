@@ -24,8 +24,8 @@ import time
 import numpy as np
 import torch
 
-from . import _lib
-from .vec_env import InfoView, _raw_stream
+from . import _bind, _lib
+from .vec_env import InfoView, _end_episodes
 
 # the attributes _params() reads: assigning one drops the cached step arguments
 _PARAM_ATTRS = frozenset(("training", "norm_obs", "norm_reward", "gamma", "clip_obs", "clip_reward", "epsilon",
@@ -65,10 +65,12 @@ class DeviceVecNormalize:
         self._stats = torch.empty(int(self.lib.he_vecnorm_stats_len(D)), dtype=torch.float64, device=dev)
         self._scratch = torch.zeros(int(self.lib.he_vecnorm_scratch_bytes(n, D)), dtype=torch.uint8, device=dev)
         self._returns = torch.zeros(n, dtype=torch.float64, device=dev)
-        # normalized obs | normalized reward in one buffer (one host copy per step_wait)
-        self._io_out = torch.empty(n * (D + 1) * 4, dtype=torch.uint8, device=dev)
-        self._obs_out = self._io_out[:n * D * 4].view(torch.float32).view(n, D)
-        self._rew_out = self._io_out[n * D * 4:].view(torch.float32)
+        # normalized obs | normalized reward in one buffer (one host copy per step_wait): the
+        # [obs | reward] head of the env's io layout
+        L = self._layout = venv._layout
+        self._io_out = torch.empty(L.terminated, dtype=torch.uint8, device=dev)
+        self._obs_out = self._io_out[:L.reward].view(torch.float32).view(n, D)
+        self._rew_out = self._io_out[L.reward:].view(torch.float32)
         self._tobs_out = torch.empty((n, D), dtype=torch.float32, device=dev)
         self._ep_ret = torch.zeros(n, dtype=torch.float64, device=dev)
         self._ep_len = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -86,20 +88,18 @@ class DeviceVecNormalize:
         self._actions_pending = None
         self._args = None   # _call_args cache
         if self.return_numpy:
-            venv._warm_pinned([self._io_out.numel()] * 3 + [n] * 3 + [4 * D * n, 8 * n, 4 * n, venv._info_flat.numel()])
+            venv._warm_pinned([L.terminated] * 3 + [n] * 3 + [L.reward, 8 * n, 4 * n, venv._info_flat.numel()])
         self._t_start = time.time()
 
     # ------------------------------------------------------------------ plumbing
-    @staticmethod
-    def _p(t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+    _p = staticmethod(_bind.ptr)
 
     def _stream(self):
-        return _raw_stream(self.venv._dev_index)
+        return _bind.stream(self.venv._dev_index)
 
-    def _check(self, st, what):
-        if st != _lib.HE_OK:
-            raise _lib.HedgeEnvError(f"{what} failed with status {st}")
+    def _check(self, st, what, handle=None):
+        """_lib.check; handle: the env's, for the entry points that take it (they leave a message)."""
+        _lib.check(self.lib, handle, st, what)
 
     def _params(self):
         p = _lib.HeVecnormParams()
@@ -258,24 +258,18 @@ class DeviceVecNormalize:
         if not p.training:
             if not self._fusable_eval:
                 return False
-            st = self.lib.he_vecnorm_attach_eval(self.venv._h, pref, c[4])
-            if st != _lib.HE_OK:
-                msg = self.lib.he_last_error(self.venv._h)
-                raise _lib.HedgeEnvError(f"he_vecnorm_attach_eval failed with status {st}: "
-                                         f"{msg.decode() if msg else ''}")
+            h = self.venv._h
+            self._check(self.lib.he_vecnorm_attach_eval(h, pref, c[4]), "he_vecnorm_attach_eval", h)
             return "eval"
         # moments="sb3": row-order sums do not split into he_step's per-workgroup partials, so a
         # training step is he_step + he_vecnorm_step (one workgroup)
         if not self._fusable or p.moments != _lib.HE_VN_MOMENTS_F64:
             return False
-        st = self.lib.he_vecnorm_attach(self.venv._h, pref, ptrs[4], ptrs[5], ptrs[6])
         # every build has the fused path and __init__ checked the env count, so any failure
         # here is a real argument error (non-finite gamma, a bad layout): raised, not hidden
         # behind the two-launch path
-        if st != _lib.HE_OK:
-            msg = self.lib.he_last_error(self.venv._h)
-            raise _lib.HedgeEnvError(f"he_vecnorm_attach failed with status {st}: "
-                                     f"{msg.decode() if msg else ''}")
+        h = self.venv._h
+        self._check(self.lib.he_vecnorm_attach(h, pref, ptrs[4], ptrs[5], ptrs[6]), "he_vecnorm_attach", h)
         return True
 
     def close(self):
@@ -304,15 +298,13 @@ class DeviceVecNormalize:
         obs, rew, term, _ = self.step_tensors(actions)
         if not self.return_numpy:
             return obs, rew, term.bool(), InfoView(self.venv, None)
-        n = self.num_envs
         # normalized obs + reward are adjacent in _io_out: two copies (with the flags), one wait
         h, t = self.venv._pull([self._io_out, term])
         done = t.view(np.bool_)   # the kernels store 0 / 1
         infos = _NormInfoView(self, done)
         if done.any():
             infos._materialize_done(done)
-        D = _lib.HE_OBS_DIM
-        return h[:n * D * 4].view(np.float32).reshape(n, D), h[n * D * 4:].view(np.float32), done, infos
+        return (*self._layout.obs_reward(h), done, infos)
 
     def step(self, actions):
         self.step_async(actions)
@@ -361,10 +353,6 @@ class _NormInfoView(InfoView):
         # called by step_wait right after the step: this step's normalized terminal obs and
         # Monitor sums are still in the wrapper's buffers -- one pull; the rows' extra items
         # are made when read (InfoView._load -> _episode_ends)
-        w, v = self._w, self._w.venv
-        srcs = [w._tobs_out, w._ep_ret_done, w._ep_len_done]
-        if self._host is None:
-            srcs.append(self._snap if self._snap is not None else v._info_flat)
-        got = v._pull(srcs)   # one wait for all of them
-        self._host_info(got[3] if self._host is None else None)
-        self._ends = (got[0], got[1], got[2], round(time.time() - w._t_start, 6), w._monitor)
+        w = self._w
+        tobs, ep_ret, ep_len = self._pull_done([w._tobs_out, w._ep_ret_done, w._ep_len_done])   # one wait
+        self._ends = _end_episodes(w.venv, done, tobs, ep_ret, ep_len, w._t_start, w._monitor)

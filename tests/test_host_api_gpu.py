@@ -76,6 +76,58 @@ def test_numpy_path_equals_device_path_and_late_infos_keep_their_step(n, host_io
     b.close()
 
 
+@pytest.mark.parametrize("n", [2, 5])
+def test_step_pointers_are_base_plus_layout_offset_and_both_paths_write_the_same_bytes(n):
+    """The pointers he_step gets -- the device io buffer's (step_tensors) and the host-mapped block's
+    (step_host) -- are base + the IoLayout offset of (n, info keys + Monitor's hidden reward_step), and
+    a step() on one env and a step_host() on its twin leave identical bytes in the two buffers."""
+    from cantorrl_amd import _lib
+    from cantorrl_amd._layout import IoLayout
+    from cantorrl_amd.vec_env import HedgingVecEnv
+    a, b = (HedgingVecEnv(n, mode="gbm", generate=GEN, seed=21, device=DEV, monitor_keywords=MON, host_io=h, **KW)
+            for h in (False, True))
+    L = IoLayout(n, MON + ("reward_step",))
+    # the device io buffer
+    base = a._obs.data_ptr()
+    assert a._hio is None
+    assert a._info_flat.data_ptr() == base + L.info0 and a._info_flat.numel() == L.total - L.info0
+    assert a._step_args[:4] == (base, base + L.reward, base + L.terminated, base + L.truncated)
+    assert a._step_args[4] == a._tobs.data_ptr()
+    assert [a._rew.data_ptr(), a._term.data_ptr(), a._trunc.data_ptr()] == list(a._step_args[1:4])
+    assert list(a._info_t) == list(L.fields) and a._rew64 is a._info_t["reward_step"]
+    # the host-mapped block: its device address is the obs pointer, its host address the io view's
+    z = b._hio
+    d = z.step_args[1]
+    host = z.io.ctypes.data
+    assert z.step_args[:6] == (d + L.actions, d, d + L.reward, d + L.terminated, d + L.truncated, d + L.terminal_obs)
+    assert z.io.size == L.total and z.act.shape == (n, 2) and z.tobs.shape == (n, 13)
+    assert z.act.ctypes.data == host + L.actions and z.tobs.ctypes.data == host + L.terminal_obs
+    assert (z.d_flag, z.h_flag) == (d + L.flag, host + L.flag)
+    assert a._step_args[5]._obj is a._info and z.step_args[6]._obj is z.info   # byref of the struct checked below
+    for info, start in ((a._info, base), (z.info, d)):
+        for k, _ in _lib.INFO_FIELDS:
+            assert getattr(info, k) == (start + L.fields[k][1] if k in L.fields else None), k
+    spans = [(0, L.truncated + n)] + [(o, o + nb) for _, o, nb in L.fields.values()]   # every byte a step writes
+    # twin envs, the same actions: identical bytes through either path, episode ends included
+    oa, ob = a.reset(), b.reset()
+    assert np.array_equal(oa, ob)
+    rng = np.random.default_rng(5)
+    for s in range(6):
+        act = rng.uniform(-1, 1, size=(n, 2)).astype(np.float32)
+        obs, rew, done, _ = a.step(act)
+        io = b.step_host(act).io
+        dev = a._io.cpu().numpy()
+        for lo, hi in spans:
+            assert dev[lo:hi].tobytes() == io[lo:hi].tobytes(), (s, lo)
+        o2, r2, d2 = L.unpack(io)
+        assert obs.tobytes() == o2.tobytes() and rew.tobytes() == r2.tobytes() and np.array_equal(done, d2)
+        assert done.all() == (s == 4)
+        if done.any():
+            assert a._tobs.cpu().numpy().tobytes() == b._hio.tobs.tobytes()
+    a.close()
+    b.close()
+
+
 def test_single_env_step_matches_vector_env_and_holds_no_aliases():
     """HedgingEnv.step's one copy per step returns the same obs / reward / info as the
     vector env's device path, and its returned obs is a private array."""
