@@ -323,8 +323,10 @@ __global__ void __launch_bounds__(kMcThreads) mc_kernel(McArgs a) {
         __asm__ volatile("" ::: "memory");
         // Re W in registers (every X_j reads all of it); Im W is drawn as the steps
         // consume it.  f64 normals: blocks [0, MO/2) give Re W pairs, [MO/2, MO) Im W
-        // pairs; f32 normals: [0, MO/4) Re W quads, [MO/4, MO/2) Im W quads.
+        // pairs; f32 normals: [0, MO/4) Re W quads, [MO/4, MO/2) Im W quads -- but a 2-point
+        // grid has half a quad of each, so its one block m holds Re W0, Re W1, Im W0.
         double w1[MO];
+        double w2q[4] = {0.0, 0.0, 0.0, 0.0};
         const double* wp = (NORM == 2) ? a.W + ((o * a.n_mc + m) * (int64_t)MO) * 2 : nullptr;
         if (NORM == 2) {
 #pragma unroll
@@ -335,6 +337,12 @@ __global__ void __launch_bounds__(kMcThreads) mc_kernel(McArgs a) {
                 __builtin_amdgcn_sched_barrier(0);
                 normal_pair_mc(rb_ctr((uint32_t)(m * MO + b), kDomMc, sub, gid), a.k0, a.k1, &w1[2 * b], &w1[2 * b + 1]);
             }
+        } else if (MO == 2) {
+            double q[4];
+            normal_quad32(rb_ctr((uint32_t)m, kDomMc, sub, gid), a.k0, a.k1, q);
+            w1[0] = q[0];
+            w1[1] = q[1];
+            w2q[0] = q[2];
         } else {
 #pragma unroll
             for (int b = 0; b < MO / 4; ++b) {
@@ -346,7 +354,6 @@ __global__ void __launch_bounds__(kMcThreads) mc_kernel(McArgs a) {
         // chunk's j, k outer (lam_k one LDS broadcast feeding kXc FMAs), then the chunk's
         // Euler steps.  Only kXc accumulators live beside Re W: 4 waves per SIMD.
         double L = 0.0;
-        double w2q[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int j0 = 0; j0 < MO - 1; j0 += kXc) {
             if (FULL ? (j0 < MO - 2) : (j0 < a.n)) {
@@ -374,7 +381,7 @@ __global__ void __launch_bounds__(kMcThreads) mc_kernel(McArgs a) {
                                             a.k1, &w2q[0], &w2q[1]);
                             w2 = w2q[j & 1];
                         } else {
-                            if ((j & 3) == 0)
+                            if (MO > 2 && (j & 3) == 0)
                                 normal_quad32(rb_ctr((uint32_t)(m * (MO / 2) + MO / 4 + j / 4), kDomMc, sub, gid),
                                               a.k0, a.k1, w2q);
                             w2 = w2q[j & 3];

@@ -29,6 +29,14 @@
  *   domain 2  main-path W_j, block j
  *   domain 3  option MC, block = mc_path * M_opt + b (f64 normals) or
  *             mc_path * M_opt / 2 + b (f32 normals); sub = day * 2 + type
+ *             f64: b < M_opt / 2 holds the pair (Re W_2b, Re W_2b+1), b = M_opt / 2 + j / 2
+ *                  the pair (Im W_j, Im W_j+1) for even j
+ *             f32: b < M_opt / 4 holds the quad Re W_4b..4b+3, b = M_opt / 4 + j / 4 the
+ *                  quad Im W_j..j+3 for j = 0 mod 4; M_opt = 2 (a one-step option) has one
+ *                  block per MC path, whose quad is (Re W_0, Re W_1, Im W_0, unused)
+ * sub is taken mod 2^24.  A pair is (r cos 2 pi u2, r sin 2 pi u2), r = sqrt(-2 ln u1), on
+ * u1 = u01(x, y), u2 = u01(z, w) of the block's words; a quad is (ra cos 2 pi u2,
+ * ra sin 2 pi u2, rb cos 2 pi u4, rb sin 2 pi u4) on u1..u4 of x, y, z, w.
  *
  * Conventions: every pointer passed to a device entry is device memory; calls are
  * stream-ordered and asynchronous (no host sync inside); arrays are row-major f64.
@@ -54,8 +62,10 @@ typedef enum rb_status {
 typedef enum rb_option_type { RB_CALL = 0, RB_PUT = 1 } rb_option_type;
 
 /* Normals of the MC option pricer: f64 Box-Muller on 53-bit uniforms (the
- * reference's precision) or f32 Box-Muller on 32-bit uniforms (4 normals per
- * Philox block; tails truncated at 6.66 sigma). */
+ * reference's precision) or f32 Box-Muller on 24-bit uniforms ((word >> 8) + 1/2) 2^-24
+ * formed in f32 (4 normals per Philox block; the smallest uniform is 2^-25, so the tails
+ * are truncated at sqrt(50 ln 2) = 5.89 sigma; the + 1/2 rounds to even above 2^23, so
+ * u = 1 and a zero radius occur). */
 typedef enum rb_normals { RB_NORMALS_F64 = 0, RB_NORMALS_F32 = 1 } rb_normals;
 
 typedef struct rb_base_params {
