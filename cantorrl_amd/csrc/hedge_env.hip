@@ -34,6 +34,7 @@
 #include <new>
 #include <type_traits>
 
+#include "vn_apply.h"
 #include "vn_moments.h"
 #include <string>
 #include <vector>
@@ -1967,10 +1968,8 @@ struct StepIo {
     uint32_t* sig_cnt;
     uint32_t sig_seq;
 };
-template <int MODE, bool BOOK, bool FAST, bool GS>
-__global__ __launch_bounds__(kBlock) void step1_kernel(const Params* __restrict__ pc, int64_t n, const float4* tA,
-                                                       const float4* tB, const double* tC, State s, StepIo sio,
-                                                       int slot0) {
+// keep_signal = false: more work follows the step in the launch
+__device__ __forceinline__ Io io_of(const StepIo& sio, bool keep_signal) {
     Io io;
     io.act = sio.act;
     io.obs = sio.obs;
@@ -1981,9 +1980,16 @@ __global__ __launch_bounds__(kBlock) void step1_kernel(const Params* __restrict_
     io.info = he_info{};
     io.pol_on = false;
     io.sums = false;
-    io.sig = sio.sig;
+    io.sig = keep_signal ? sio.sig : nullptr;
     io.sig_cnt = sio.sig_cnt;
     io.sig_seq = sio.sig_seq;
+    return io;
+}
+template <int MODE, bool BOOK, bool FAST, bool GS>
+__global__ __launch_bounds__(kBlock) void step1_kernel(const Params* __restrict__ pc, int64_t n, const float4* tA,
+                                                       const float4* tB, const double* tC, State s, StepIo sio,
+                                                       int slot0) {
+    const Io io = io_of(sio, true);
     step_body<MODE, false, true, BOOK, FAST, false, GS>(*pc, n, tA, tB, tC, s, io, 1, slot0, blockIdx.x);
 }
 
@@ -1996,17 +2002,7 @@ template <int MODE, bool BOOK, bool FAST, bool GS>
 __global__ __launch_bounds__(kBlock) void step1_vn_kernel(const Params* __restrict__ pc, int64_t n, const float4* tA,
                                                           const float4* tB, const double* tC, State s, StepIo sio,
                                                           int slot0, vn::MomentsArgs vm) {
-    Io io;
-    io.act = sio.act;
-    io.obs = sio.obs;
-    io.rew = sio.rew;
-    io.term = sio.term;
-    io.trunc = sio.trunc;
-    io.tobs = sio.tobs;
-    io.info = he_info{};
-    io.pol_on = false;
-    io.sums = false;
-    io.sig = nullptr;  // more work follows the step in this launch
+    const Io io = io_of(sio, false);
     // this thread's env (kEpw == 64: env = workgroup base + threadIdx.x): its running return
     // is loaded before the step, so the moments need no further memory round trip
     static_assert(kEpw == 64 && kEpb == kBlock, "one env per thread");
@@ -2026,17 +2022,7 @@ template <int MODE, bool BOOK, bool FAST, bool GS>
 __global__ __launch_bounds__(kBlock) void step1_vne_kernel(const Params* __restrict__ pc, int64_t n, const float4* tA,
                                                            const float4* tB, const double* tC, State s, StepIo sio,
                                                            int slot0, vn::ApplyArgs va) {
-    Io io;
-    io.act = sio.act;
-    io.obs = sio.obs;
-    io.rew = sio.rew;
-    io.term = sio.term;
-    io.trunc = sio.trunc;
-    io.tobs = sio.tobs;
-    io.info = he_info{};
-    io.pol_on = false;
-    io.sums = false;
-    io.sig = nullptr;
+    const Io io = io_of(sio, false);
     static_assert(kEpw == 64 && kEpb == kBlock, "one env per thread");
     const int64_t r0 = (int64_t)blockIdx.x * kEpb;
     __shared__ vn::FrozenNorm fz;
@@ -5371,16 +5357,9 @@ he_status he_vecnorm_attach(he_env* env, const he_vecnorm_params* p, double* ret
     if (env->cfg.n_envs > (int64_t)vn::kVnMaxBlocks * kEpb)
         return fail(env, HE_EINVAL, "he_vecnorm_attach covers up to %d envs (use he_vecnorm_step)",
                     vn::kVnMaxBlocks * kEpb);
-    vn::MomentsArgs m = {};
-    m.n = env->cfg.n_envs;
+    vn::MomentsArgs m = vn::moments_args(p, env->cfg.n_envs, returns, stats, scratch);
     m.rows_per_block = kEpb;
-    m.upd_obs = p->training && p->norm_obs;
-    m.upd_ret = p->training != 0;
     m.shift_mean = 1;
-    m.gamma = p->gamma;
-    m.returns = returns;
-    m.stats = stats;
-    m.part = (double*)scratch;
     env->vn = m;
     env->vn_on = m.upd_obs || m.upd_ret;
     return HE_OK;
@@ -5405,23 +5384,7 @@ he_status he_vecnorm_attach_eval(he_env* env, const he_vecnorm_params* p, const 
         return fail(env, HE_EINVAL, "he_vecnorm_out: the Monitor buffers come together");
     if (kEpb != vn::kVnChunk)
         return fail(env, HE_EINVAL, "he_vecnorm_attach_eval needs 256 envs per step workgroup");
-    vn::ApplyArgs a = {};
-    a.norm_obs = p->norm_obs != 0;
-    a.norm_reward = p->norm_reward != 0;
-    a.sb3 = p->moments == HE_VN_MOMENTS_SB3;
-    a.clip_obs = p->clip_obs;
-    a.clip_rew = p->clip_reward;
-    a.eps = p->epsilon;
-    a.stats = out->stats;
-    a.returns = out->returns;
-    a.obs_out = out->obs_out;
-    a.rew_out = out->reward_out;
-    a.tobs_out = out->terminal_obs_out;
-    a.ep_ret = out->ep_return;
-    a.ep_len = out->ep_length;
-    a.ep_ret_done = out->ep_return_done;
-    a.ep_len_done = out->ep_length_done;
-    env->vne = a;
+    env->vne = vn::apply_args(p, *out);
     env->vne_p = *p;
     env->vne_on = true;
     env->vn_on = false;

@@ -23,6 +23,11 @@
 // moments = HE_VN_MOMENTS_SB3 (n <= 4096) is one launch of one workgroup instead,
 // vn_sb3_kernel: SB3's own NumPy arithmetic bit for bit (vn_sb3.h) -- the f32 row-order sums
 // of the obs columns are one dependent chain per column, which no second workgroup could help.
+//
+// This file holds the kernels, their argument block and the C entry points.  What the kernels
+// share with the epilogues fused into he_step (hedge_env.hip) and with the host mirror is in the
+// headers: the moments and the snapshot in vn_moments.h; the normalisers, the flat obs pass, a
+// row's tail and ApplyArgs in vn_apply.h; SB3's arithmetic, clipd and rms_update in vn_sb3.h.
 
 #include <hip/hip_runtime.h>
 
@@ -32,6 +37,7 @@
 #include <vector>
 
 #include "../../include/hedge_env.h"
+#include "vn_apply.h"
 #include "vn_moments.h"
 #include "vn_sb3.h"
 
@@ -44,53 +50,27 @@ using vn::kVnMaxBlocks;
 using vn::kVnThreads;
 using vn::block_sum;
 using vn::load_tile;
+using vn::ColNorm;
+using vn::col_norm;
+using vn::RowIn;
 
+// A launch's arguments: the two halves (vn_moments.h, vn_apply.h; base_args) and what only
+// these kernels read.
 struct VnArgs {
-    int64_t n;
-    int rows_per_block;
-    int blocks;
-    int training, norm_obs, norm_reward, upd_obs;
-    double gamma, clip_obs, clip_rew, eps;
-    const float* obs;
-    const float* reward;
+    vn::MomentsArgs m;         // m.upd_ret: training && !reset
+    vn::ApplyArgs a;
     const uint8_t* done;
     const float* tobs;
-    double* returns;
-    double* stats;
-    double* part;
-    float* obs_out;
-    float* rew_out;
-    float* tobs_out;
-    double* ep_ret;
-    int32_t* ep_len;
-    double* ep_ret_done;
-    int32_t* ep_len_done;
     const double* ep_reward;   // the env's f64 step rewards Monitor sums (he_info::reward_step)
+    int blocks;
     int reset;   // he_vecnorm_reset: returns = 0 instead of the discounted update
-    int sb3;     // moments = HE_VN_MOMENTS_SB3: vn_sb3_kernel
 };
-
-// RunningMeanStd.update_from_moments (SB3 common/running_mean_std.py), f64
-__device__ __forceinline__ void rms_update(double* mean, double* var, double* count, double bmean, double bvar,
-                                           double bcount) {
-    const double delta = bmean - *mean;
-    const double tot = *count + bcount;
-    const double new_mean = *mean + delta * bcount / tot;
-    const double m_a = *var * *count;
-    const double m_b = bvar * bcount;
-    const double m2 = m_a + m_b + delta * delta * *count * bcount / tot;
-    *mean = new_mean;
-    *var = m2 / tot;
-    *count = tot;
-}
-
-__device__ __forceinline__ double clipd(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 struct VnRows {
     int64_t r0, r1;
     double cnt;
 };
-__device__ __forceinline__ VnRows rows_of(const VnArgs& a) {
+__device__ __forceinline__ VnRows rows_of(const vn::MomentsArgs& a) {
     VnRows w;
     w.r0 = (int64_t)blockIdx.x * a.rows_per_block;
     w.r1 = (w.r0 + a.rows_per_block < a.n) ? w.r0 + a.rows_per_block : a.n;
@@ -102,50 +82,23 @@ __device__ __forceinline__ VnRows rows_of(const VnArgs& a) {
 // the obs shift is the batch's row 0).  The kernel boundary publishes the partials to
 // launch 2 -- no atomics, no waiting (a single launch with a grid-wide wait measured
 // 25 us at 65,536 envs: four dependent device-coherent round trips between workgroups).
-__device__ __forceinline__ vn::MomentsArgs moments_args(const VnArgs& a) {
-    vn::MomentsArgs m = {};
-    m.n = a.n;
-    m.rows_per_block = a.rows_per_block;
-    m.upd_obs = a.upd_obs;
-    m.upd_ret = a.training && !a.reset;
-    m.shift_mean = 0;
-    m.gamma = a.gamma;
-    m.obs = a.obs;
-    m.reward = a.reward;
-    m.returns = a.returns;
-    m.stats = a.stats;
-    m.part = a.part;
-    return m;
-}
-__global__ void __launch_bounds__(kVnThreads) vn_moments_kernel(VnArgs a) {
-    vn::moments_body(moments_args(a), blockIdx.x);
+__global__ void __launch_bounds__(kVnThreads) vn_moments_kernel(vn::MomentsArgs m) {
+    vn::moments_body(m, blockIdx.x);
 }
 
-// A row's inputs besides its obs: reward, done flag, Monitor running sums and the f64
-// reward Monitor adds (Monitor wraps each env inside the VecEnv, train_ppo_v2.py:119, so it
-// sums the env's own f64 reward, hedging_env_v2.py:262,294 -- not the f32 VecEnv buffer).
-struct RowIn {
-    float rw;
-    bool dn;
-    double er;
-    double rw64;
-    int32_t el;
-};
+// A row's inputs (vn::RowIn) from memory.
 __device__ __forceinline__ RowIn row_in(const VnArgs& a, int64_t r) {
     RowIn in;
-    in.rw = a.reward[r];
+    in.rw = a.m.reward[r];
     in.dn = a.done ? a.done[r] != 0 : false;
-    in.er = a.ep_ret ? a.ep_ret[r] : 0.0;
-    in.rw64 = a.ep_ret ? a.ep_reward[r] : 0.0;
-    in.el = a.ep_ret ? a.ep_len[r] : 0;
+    in.er = a.a.ep_ret ? a.a.ep_ret[r] : 0.0;
+    in.rw64 = a.a.ep_ret ? a.ep_reward[r] : 0.0;
+    in.el = a.a.ep_ret ? a.a.ep_len[r] : 0;
     return in;
 }
 
 constexpr int kMergeLanes = 8;   // lanes per merged value (vn_apply_kernel)
 static_assert(kMergeLanes * kPart <= kVnThreads, "one merge lane group per value");
-using vn::ColNorm;
-using vn::col_norm;
-using vn::norm_elem;
 
 // Launch 2: every workgroup merges all the partials itself (one block reduction in a
 // fixed order, so the same statistics everywhere; workgroup 0 stores them), then
@@ -154,40 +107,34 @@ using vn::norm_elem;
 // 7.5 / 10.2 / 15.9 us at 65,536 envs, r03s32 -- the merge's reads are not what the launch
 // waits on; each thread's rows are.)
 __global__ void __launch_bounds__(kVnThreads) vn_apply_kernel(VnArgs a) {
-    constexpr int R = 1;
     __shared__ double ssum[kPart];
     __shared__ ColNorm snorm[kD];     // per obs column (col_norm)
     __shared__ double srinv;
     __shared__ float tile[kVnChunk * kD];
-    const VnRows w = rows_of(a);
-    const float clip = (float)a.clip_obs;
-    const bool upd_ret = a.training && !a.reset;
+    const VnRows w = rows_of(a.m);
+    const vn::SplitNorm nz{snorm, &srinv, (float)a.a.clip_obs, a.a.clip_rew};
     const int t = threadIdx.x;
-    const bool resident = w.r1 - w.r0 <= kVnChunk * R;
+    const bool resident = w.r1 - w.r0 <= kVnChunk;
     const int nrows = (int)(w.r1 - w.r0);
     // the rows' loads first -- obs, and the row's reward, done flag and Monitor sums: they
     // are all in flight while the partials are merged (one memory round trip per launch)
-    float xr[R * kD];
+    float xr[kD];
     const int nres = resident ? nrows * kD : 0;
-    const float* src = a.obs + w.r0 * kD;
+    const float* src = a.m.obs + w.r0 * kD;
 #pragma unroll
-    for (int q = 0; q < R * kD; ++q) {
+    for (int q = 0; q < kD; ++q) {
         const int k = t + q * kVnThreads;
         xr[q] = k < nres ? src[k] : 0.0f;
     }
-    RowIn pin[R];
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-        pin[j] = {};
-        if (resident && !a.reset && t + j * kVnThreads < nrows) pin[j] = row_in(a, w.r0 + t + j * kVnThreads);
-    }
-    if (a.upd_obs || upd_ret) {
+    RowIn pin = {};
+    if (resident && !a.reset && t < nrows) pin = row_in(a, w.r0 + t);
+    if (a.m.upd_obs || a.m.upd_ret) {
         // the merge, transposed: thread t < 8 kPart sums value c = t / 8 of the partials
         // b = t % 8, t % 8 + 8, ... (in b order), then a butterfly over its 8-lane group --
         // no block-wide LDS reduction (the row-major block_sum stored and re-read 61 KB)
         if (t < kMergeLanes * kPart) {
             const int c = t / kMergeLanes, j = t % kMergeLanes;
-            const double* P = a.part + (size_t)c * kVnMaxBlocks;
+            const double* P = a.m.part + (size_t)c * kVnMaxBlocks;
             // every load issued before the first add (unrolled over the kVnMaxBlocks bound):
             // a rolled loop waited one round trip per partial
             double v[kVnMaxBlocks / kMergeLanes];
@@ -206,7 +153,7 @@ __global__ void __launch_bounds__(kVnThreads) vn_apply_kernel(VnArgs a) {
         __syncthreads();
         const int c = t;
         if (c <= kD) {
-            const double* old = a.part + kVnMaxBlocks * kPart;   // launch 1's snapshot
+            const double* old = a.m.part + kVnMaxBlocks * kPart;   // launch 1's snapshot
             const double n_a = ssum[0], s1 = ssum[1 + c], s2 = ssum[2 + kD + c];
             // np.mean / np.var(ddof=0) of the batch from the shifted sums, then
             // RunningMeanStd.update_from_moments
@@ -215,87 +162,55 @@ __global__ void __launch_bounds__(kVnThreads) vn_apply_kernel(VnArgs a) {
             const double var_a = (m2 > 0.0 ? m2 : 0.0) / n_a;
             const int im = (c < kD) ? c : 2 * kD + 1, iv = (c < kD) ? kD + c : 2 * kD + 2;
             double mean = old[im], var = old[iv];
-            if ((c < kD && a.upd_obs) || (c == kD && upd_ret)) {
+            if ((c < kD && a.m.upd_obs) || (c == kD && a.m.upd_ret)) {
                 double count = (c < kD) ? old[2 * kD] : old[2 * kD + 3];
-                rms_update(&mean, &var, &count, mean_a, var_a, n_a);
+                sb3::rms_update(&mean, &var, &count, mean_a, var_a * n_a, n_a);
                 if (blockIdx.x == 0) {
-                    if (c == 0) a.stats[2 * kD] = count;
-                    if (c == kD) a.stats[2 * kD + 3] = count;
-                    a.stats[im] = mean;
-                    a.stats[iv] = var;
+                    if (c == 0) a.m.stats[2 * kD] = count;
+                    if (c == kD) a.m.stats[2 * kD + 3] = count;
+                    a.m.stats[im] = mean;
+                    a.m.stats[iv] = var;
                 }
             }
             if (c < kD) {
-                snorm[c] = col_norm(mean, var, a.eps);
+                snorm[c] = col_norm(mean, var, a.a.eps);
             } else {
-                srinv = 1.0 / sqrt(var + a.eps);
+                srinv = 1.0 / sqrt(var + a.a.eps);
             }
         }
         __syncthreads();
     } else {
-        if (t < kD) snorm[t] = col_norm(a.stats[t], a.stats[kD + t], a.eps);
-        if (t == 0) srinv = 1.0 / sqrt(a.stats[2 * kD + 2] + a.eps);
+        if (t < kD) snorm[t] = col_norm(a.m.stats[t], a.m.stats[kD + t], a.a.eps);
+        if (t == 0) srinv = 1.0 / sqrt(a.m.stats[2 * kD + 2] + a.a.eps);
         __syncthreads();
     }
     // the rows' own work (reward, returns, terminal obs, Monitor): thread t, row r0 + t
     auto row_work = [&](int64_t r, const RowIn& in) {
-        if (a.reset) {
-            a.returns[r] = 0.0;
-            return;
-        }
-        const bool dn = in.dn;
-        const float rw = in.rw;
-        a.rew_out[r] = a.norm_reward ? (float)clipd((double)rw * srinv, -a.clip_rew, a.clip_rew) : rw;
-        if (dn && a.tobs && a.tobs_out) {   // rare: per-row accesses
-#pragma unroll
-            for (int c = 0; c < kD; ++c) {
-                const float x = a.tobs[r * kD + c];
-                a.tobs_out[r * kD + c] = a.norm_obs ? norm_elem(x, snorm[c], clip) : x;
-            }
-        }
-        if (dn) a.returns[r] = 0.0;   // self.returns[dones] = 0
-        if (a.ep_ret) {                 // Monitor: sum(rewards) of the f64 rewards, len(rewards)
-            const double er = in.er + in.rw64;
-            const int32_t el = in.el + 1;
-            if (dn) {
-                a.ep_ret_done[r] = er;
-                a.ep_len_done[r] = el;
-            }
-            a.ep_ret[r] = dn ? 0.0 : er;
-            a.ep_len[r] = dn ? 0 : el;
-        }
+        if (a.reset)
+            a.m.returns[r] = 0.0;
+        else
+            vn::row_tail(a.a, nz, a.tobs, r, in);
     };
     if (resident) {
-        // the obs element-wise straight from the registers the loads landed in: element
-        // k = t + 256 q of the slice is column k % 13 (the slice starts at a row boundary),
-        // stepped by 256 % 13 = 9 per q without a division
-        float* dst = a.obs_out + w.r0 * kD;
-        int c = t % kD;
-#pragma unroll
-        for (int q = 0; q < R * kD; ++q) {
-            const int k = t + q * kVnThreads;
-            if (k < nres) dst[k] = a.norm_obs ? norm_elem(xr[q], snorm[c], clip) : xr[q];
-            c += kVnThreads % kD;
-            c = c >= kD ? c - kD : c;
-        }
-#pragma unroll
-        for (int j = 0; j < R; ++j)
-            if (t + j * kVnThreads < nrows) row_work(w.r0 + t + j * kVnThreads, pin[j]);
+        // the obs element-wise straight from the registers the loads landed in
+        vn::obs_pass<vn::kUnrolled>(a.a.obs_out + w.r0 * kD, nres, a.a.norm_obs != 0, nz,
+                                    [&xr](int q, int) { return xr[q]; });
+        if (t < nrows) row_work(w.r0 + t, pin);
         return;
     }
     for (int64_t c0 = w.r0; c0 < w.r1; c0 += kVnChunk) {
         const int rows = (int)((w.r1 - c0) < kVnChunk ? (w.r1 - c0) : kVnChunk);
-        load_tile(tile, a.obs, c0, rows);
+        load_tile(tile, a.m.obs, c0, rows);
         if (t < rows) {
             // the row in place in LDS, then stored back as a flat coalesced copy
-            if (a.norm_obs) {
+            if (a.a.norm_obs) {
 #pragma unroll
-                for (int c = 0; c < kD; ++c) tile[t * kD + c] = norm_elem(tile[t * kD + c], snorm[c], clip);
+                for (int c = 0; c < kD; ++c) tile[t * kD + c] = nz.obs(tile[t * kD + c], c);
             }
             row_work(c0 + t, a.reset ? RowIn{} : row_in(a, c0 + t));
         }
         __syncthreads();
-        float* dst = a.obs_out + c0 * kD;
+        float* dst = a.a.obs_out + c0 * kD;
         const int nf = rows * kD;
         for (int k = t; k < nf; k += kVnThreads) dst[k] = tile[k];
         __syncthreads();
@@ -321,14 +236,14 @@ __global__ void __launch_bounds__(kVnThreads) vn_sb3_kernel(VnArgs a) {
     __shared__ double nval[sb3::kNodes];   // the pairwise tree's node sums, heap order
     __shared__ double smean[kD], ssd[kD], srsd;
     const int t = threadIdx.x;
-    const int n = (int)a.n;
-    const bool upd_ret = a.training && !a.reset;
+    const int n = (int)a.m.n;
+    const bool upd_ret = a.m.upd_ret;
     double bret[2] = {0.0, 1.0};   // the returns' batch mean and variance (every thread)
     // every load that depends on nothing first, in flight together: the first obs chunk, the
     // thread's first row (reward, done flag, Monitor sums, running return) and the statistics
     float nx[kD];
     auto fetch = [&](int ch) {
-        const float* src = a.obs + (size_t)ch * kVnChunk * kD;
+        const float* src = a.m.obs + (size_t)ch * kVnChunk * kD;
         const int nf = (n - ch * kVnChunk < kVnChunk ? n - ch * kVnChunk : kVnChunk) * kD;
 #pragma unroll
         for (int q = 0; q < kD; ++q) {
@@ -337,25 +252,25 @@ __global__ void __launch_bounds__(kVnThreads) vn_sb3_kernel(VnArgs a) {
         }
     };
     const bool tile_all = n <= kVnChunk;   // the whole batch is the first chunk: nx serves the apply too
-    if (a.upd_obs || tile_all) fetch(0);
+    if (a.m.upd_obs || tile_all) fetch(0);
     RowIn pin = {};
     if (!a.reset && t < n) pin = row_in(a, t);
-    double ret0 = upd_ret && t < n ? a.returns[t] : 0.0;
+    double ret0 = upd_ret && t < n ? a.m.returns[t] : 0.0;
     double st_mean = 0.0, st_var = 1.0, st_count = 0.0;   // lanes 0 .. 12 an obs column, lane 13 the returns
     if (t < kD) {
-        st_mean = a.stats[t];
-        st_var = a.stats[kD + t];
-        st_count = a.stats[2 * kD];
+        st_mean = a.m.stats[t];
+        st_var = a.m.stats[kD + t];
+        st_count = a.m.stats[2 * kD];
     } else if (t == kD) {
-        st_mean = a.stats[2 * kD + 1];
-        st_var = a.stats[2 * kD + 2];
-        st_count = a.stats[2 * kD + 3];
+        st_mean = a.m.stats[2 * kD + 1];
+        st_var = a.m.stats[2 * kD + 2];
+        st_count = a.m.stats[2 * kD + 3];
     }
     if (upd_ret) {
         for (int r = t; r < n; r += kVnThreads) {
-            const double ret = r == t ? sb3::ret_update(ret0, a.gamma, pin.rw)
-                                      : sb3::ret_update(a.returns[r], a.gamma, a.reward[r]);
-            a.returns[r] = ret;
+            const double ret = r == t ? sb3::ret_update(ret0, a.m.gamma, pin.rw)
+                                      : sb3::ret_update(a.m.returns[r], a.m.gamma, a.m.reward[r]);
+            a.m.returns[r] = ret;
             rbuf[r] = ret;
         }
         // thread t is node t of the pairwise tree: a leaf, a split or (most) nothing
@@ -380,7 +295,7 @@ __global__ void __launch_bounds__(kVnThreads) vn_sb3_kernel(VnArgs a) {
         }
     }
     float bmean = 0.0f, bvar = 0.0f;   // lanes 0 .. 12: np.mean / np.var of their obs column
-    if (a.upd_obs) {
+    if (a.m.upd_obs) {
         const int nchunks = (n + kVnChunk - 1) / kVnChunk;
         const int iters = nchunks == 1 ? 1 : 2 * nchunks;   // one chunk serves both passes from LDS
         float s = 0.0f, v = 0.0f;
@@ -404,70 +319,36 @@ __global__ void __launch_bounds__(kVnThreads) vn_sb3_kernel(VnArgs a) {
     }
     // the 14 statistics: RunningMeanStd.update_from_moments, stored, and the columns' constants
     if (t < kD) {
-        if (a.upd_obs) {
+        if (a.m.upd_obs) {
             sb3::rms_update(&st_mean, &st_var, &st_count, (double)bmean, sb3::batch_m2_obs(bvar, n), (double)n);
-            a.stats[t] = st_mean;
-            a.stats[kD + t] = st_var;
-            if (t == 0) a.stats[2 * kD] = st_count;
+            a.m.stats[t] = st_mean;
+            a.m.stats[kD + t] = st_var;
+            if (t == 0) a.m.stats[2 * kD] = st_count;
         }
         smean[t] = st_mean;
-        ssd[t] = sb3::norm_sd(st_var, a.eps);
+        ssd[t] = sb3::norm_sd(st_var, a.a.eps);
     } else if (t == kD) {
         if (upd_ret) {
             sb3::rms_update(&st_mean, &st_var, &st_count, bret[0], bret[1] * (double)n, (double)n);
-            a.stats[2 * kD + 1] = st_mean;
-            a.stats[2 * kD + 2] = st_var;
-            a.stats[2 * kD + 3] = st_count;
+            a.m.stats[2 * kD + 1] = st_mean;
+            a.m.stats[2 * kD + 2] = st_var;
+            a.m.stats[2 * kD + 3] = st_count;
         }
-        srsd = sb3::norm_sd(st_var, a.eps);
+        srsd = sb3::norm_sd(st_var, a.a.eps);
     }
     __syncthreads();
-    // the obs element-wise, flat and coalesced: element k is column k % 13, stepped by
-    // 256 % 13 = 9 per trip without a division
-    {
-        const int nf = n * kD;
-        int c = t % kD;
-        if (tile_all) {   // the thread's elements are still in its registers
-#pragma unroll
-            for (int q = 0; q < kD; ++q) {
-                const int k = t + q * kVnThreads;
-                if (k < nf) a.obs_out[k] = a.norm_obs ? sb3::norm_obs(nx[q], smean[c], ssd[c], a.clip_obs) : nx[q];
-                c += kVnThreads % kD;
-                c = c >= kD ? c - kD : c;
-            }
-        } else {
-            for (int k = t; k < nf; k += kVnThreads) {
-                const float x = a.obs[k];
-                a.obs_out[k] = a.norm_obs ? sb3::norm_obs(x, smean[c], ssd[c], a.clip_obs) : x;
-                c += kVnThreads % kD;
-                c = c >= kD ? c - kD : c;
-            }
-        }
+    const vn::Sb3Norm nz{smean, ssd, &srsd, a.a.clip_obs, a.a.clip_rew};
+    if (tile_all) {   // the thread's elements are still in its registers
+        vn::obs_pass<vn::kUnrolled>(a.a.obs_out, n * kD, a.a.norm_obs != 0, nz, [&nx](int q, int) { return nx[q]; });
+    } else {
+        const float* obs = a.m.obs;
+        vn::obs_pass<vn::kStrided>(a.a.obs_out, n * kD, a.a.norm_obs != 0, nz, [obs](int, int k) { return obs[k]; });
     }
     for (int r = t; r < n; r += kVnThreads) {
-        if (a.reset) {
-            a.returns[r] = 0.0;
-            continue;
-        }
-        const RowIn in = r == t ? pin : row_in(a, r);
-        a.rew_out[r] = a.norm_reward ? sb3::norm_rew(in.rw, srsd, a.clip_rew) : in.rw;
-        if (in.dn && a.tobs && a.tobs_out) {   // rare: per-row accesses
-            for (int c = 0; c < kD; ++c) {
-                const float x = a.tobs[(size_t)r * kD + c];
-                a.tobs_out[(size_t)r * kD + c] = a.norm_obs ? sb3::norm_obs(x, smean[c], ssd[c], a.clip_obs) : x;
-            }
-        }
-        if (in.dn) a.returns[r] = 0.0;   // self.returns[dones] = 0
-        if (a.ep_ret) {                    // Monitor: sum(rewards) of the f64 rewards, len(rewards)
-            const double er = in.er + in.rw64;
-            const int32_t el = in.el + 1;
-            if (in.dn) {
-                a.ep_ret_done[r] = er;
-                a.ep_len_done[r] = el;
-            }
-            a.ep_ret[r] = in.dn ? 0.0 : er;
-            a.ep_len[r] = in.dn ? 0 : el;
-        }
+        if (a.reset)
+            a.m.returns[r] = 0.0;
+        else
+            vn::row_tail(a.a, nz, a.tobs, r, r == t ? pin : row_in(a, r));
     }
 }
 
@@ -491,18 +372,17 @@ __global__ void init_kernel(double* stats) {
     }
 }
 
-he_status launch(VnArgs& a, void* scratch, hipStream_t s, bool moments = true) {
-    if (a.sb3) {   // the whole step in one workgroup (the caller checked n <= sb3::kMaxN)
+he_status launch(VnArgs& a, hipStream_t s, bool moments = true) {
+    if (a.a.sb3) {   // the whole step in one workgroup (the caller checked n <= sb3::kMaxN)
         a.blocks = 1;
-        a.rows_per_block = (int)a.n;
+        a.m.rows_per_block = (int)a.m.n;
         hipLaunchKernelGGL(vn_sb3_kernel, dim3(1), dim3(kVnThreads), 0, s, a);
         return hipGetLastError() == hipSuccess ? HE_OK : HE_EHIP;
     }
-    a.blocks = blocks_for(a.n);
-    a.rows_per_block = (int)((a.n + a.blocks - 1) / a.blocks);
-    a.part = (double*)scratch;   // [kVnMaxBlocks][kPart] partials, then the old statistics
-    if (moments && (a.upd_obs || (a.training && !a.reset))) {
-        hipLaunchKernelGGL(vn_moments_kernel, dim3(a.blocks), dim3(kVnThreads), 0, s, a);
+    a.blocks = blocks_for(a.m.n);
+    a.m.rows_per_block = (int)((a.m.n + a.blocks - 1) / a.blocks);
+    if (moments && (a.m.upd_obs || a.m.upd_ret)) {
+        hipLaunchKernelGGL(vn_moments_kernel, dim3(a.blocks), dim3(kVnThreads), 0, s, a.m);
         if (hipGetLastError() != hipSuccess) return HE_EHIP;
     }
     hipLaunchKernelGGL(vn_apply_kernel, dim3(a.blocks), dim3(kVnThreads), 0, s, a);
@@ -518,18 +398,16 @@ bool count_ok(const he_vecnorm_params* p, int64_t n) {
     return p->moments != HE_VN_MOMENTS_SB3 || n <= sb3::kMaxN;
 }
 
-VnArgs base_args(const he_vecnorm_params* p, int64_t n) {
+// The two halves of a launch over n rows of obs (reward NULL: he_vecnorm_reset); out.stats = stats.
+VnArgs base_args(const he_vecnorm_params* p, int64_t n, const float* obs, const float* reward, double* stats,
+                 void* scratch, const he_vecnorm_out& out) {
     VnArgs a = {};
-    a.n = n;
-    a.training = p->training != 0;
-    a.norm_obs = p->norm_obs != 0;
-    a.norm_reward = p->norm_reward != 0;
-    a.upd_obs = a.training && a.norm_obs;
-    a.gamma = p->gamma;
-    a.clip_obs = p->clip_obs;
-    a.clip_rew = p->clip_reward;
-    a.eps = p->epsilon;
-    a.sb3 = p->moments == HE_VN_MOMENTS_SB3;
+    a.reset = reward == nullptr;
+    a.m = vn::moments_args(p, n, out.returns, stats, scratch);
+    a.m.upd_ret = a.m.upd_ret && !a.reset;
+    a.m.obs = obs;
+    a.m.reward = reward;
+    a.a = vn::apply_args(p, out);
     return a;
 }
 
@@ -582,22 +460,13 @@ static he_status vecnorm_step(const he_vecnorm_params* p, int64_t n, const float
     if ((ep_return != nullptr) != (ep_length != nullptr) ||
         (ep_return && (!ep_return_done || !ep_length_done || !done || !ep_reward)))
         return HE_EINVAL;
-    VnArgs a = base_args(p, n);
-    a.obs = obs;
-    a.reward = reward;
+    VnArgs a = base_args(p, n, obs, reward, stats, scratch,
+                         he_vecnorm_out{stats, returns, obs_out, reward_out, terminal_obs_out, ep_return, ep_length,
+                                        ep_return_done, ep_length_done});
     a.done = done;
     a.tobs = terminal_obs;
-    a.returns = returns;
-    a.stats = stats;
-    a.obs_out = obs_out;
-    a.rew_out = reward_out;
-    a.tobs_out = terminal_obs_out;
-    a.ep_ret = ep_return;
-    a.ep_len = ep_length;
-    a.ep_ret_done = ep_return_done;
-    a.ep_len_done = ep_length_done;
     a.ep_reward = ep_reward;
-    return launch(a, scratch, (hipStream_t)stream, moments);
+    return launch(a, (hipStream_t)stream, moments);
 }
 
 he_status he_vecnorm_step(const he_vecnorm_params* p, int64_t n, const float* obs, const float* reward,
@@ -627,13 +496,12 @@ he_status he_vecnorm_reset(const he_vecnorm_params* p, int64_t n, const float* o
     if (!params_ok(p) || n < 0 || !count_ok(p, n)) return HE_EINVAL;
     if (n == 0) return HE_OK;
     if (!obs || !returns || !stats || !scratch || !obs_out) return HE_EINVAL;
-    VnArgs a = base_args(p, n);
-    a.reset = 1;
-    a.obs = obs;
-    a.returns = returns;
-    a.stats = stats;
-    a.obs_out = obs_out;
-    return launch(a, scratch, (hipStream_t)stream);
+    he_vecnorm_out out = {};
+    out.stats = stats;
+    out.returns = returns;
+    out.obs_out = obs_out;
+    VnArgs a = base_args(p, n, obs, nullptr, stats, scratch, out);
+    return launch(a, (hipStream_t)stream);
 }
 
 he_status he_host_vecnorm_sb3(const he_vecnorm_params* p, int64_t n64, const float* obs, const float* reward,
@@ -683,19 +551,19 @@ he_status he_host_vecnorm_sb3(const he_vecnorm_params* p, int64_t n64, const flo
     const double rsd = sb3::norm_sd(stats[2 * kD + 2], p->epsilon);
     for (int k = 0; k < n * kD; ++k)
         obs_out[k] = norm_obs ? sb3::norm_obs(obs[k], stats[k % kD], sd[k % kD], p->clip_obs) : obs[k];
+    const vn::Sb3Norm nz{stats, sd, &rsd, p->clip_obs, p->clip_reward};
+    he_vecnorm_out out = {};   // no Monitor
+    out.stats = stats;
+    out.returns = returns;
+    out.obs_out = obs_out;
+    out.reward_out = reward_out;
+    out.terminal_obs_out = terminal_obs_out;
+    const vn::ApplyArgs a = vn::apply_args(p, out);
     for (int r = 0; r < n; ++r) {
-        if (reset) {
+        if (reset)
             returns[r] = 0.0;
-            continue;
-        }
-        reward_out[r] = p->norm_reward ? sb3::norm_rew(reward[r], rsd, p->clip_reward) : reward[r];
-        const bool dn = done && done[r];
-        if (dn && terminal_obs && terminal_obs_out)
-            for (int c = 0; c < kD; ++c) {
-                const float x = terminal_obs[(size_t)r * kD + c];
-                terminal_obs_out[(size_t)r * kD + c] = norm_obs ? sb3::norm_obs(x, stats[c], sd[c], p->clip_obs) : x;
-            }
-        if (dn) returns[r] = 0.0;
+        else
+            vn::row_tail(a, nz, terminal_obs, r, RowIn{reward[r], done && done[r], 0.0, 0.0, 0});
     }
     return HE_OK;
 }

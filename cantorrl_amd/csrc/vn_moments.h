@@ -7,8 +7,9 @@
 // Per workgroup of kVnThreads threads and up to rows_per_block rows: one pass of f64 sums
 // S1 = sum d and S2 = sum d^2 with d = x - shift over the 13 obs columns and the updated
 // running returns, stored as partial [kPart][kVnMaxBlocks] (count, S1[D + 1], S2[D + 1]);
-// workgroup 0 also stores a snapshot of the old statistics and the shifts, which
-// vn_apply_kernel (vecnorm.hip) reads after the kernel boundary.
+// workgroup 0 also stores a snapshot of the old statistics and the shifts (store_snapshot),
+// which vn_apply_kernel (vecnorm.hip) reads after the kernel boundary.  The second half of the
+// step -- normalisers, obs pass, a row's tail, the fused eval step -- is vn_apply.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -37,9 +38,22 @@ struct MomentsArgs {
     const float* obs;
     const float* reward;
     double* returns;
-    const double* stats;
+    double* stats;           // read here; the merge (vn_apply_kernel, vn_sb3_kernel) stores the update
     double* part;
 };
+// The half's arguments from the caller's parameters and buffers (host).  The site adds what is
+// its own: rows_per_block, shift_mean, the obs and reward of the launch.
+inline MomentsArgs moments_args(const he_vecnorm_params* p, int64_t n, double* returns, double* stats, void* scratch) {
+    MomentsArgs m = {};
+    m.n = n;
+    m.upd_obs = p->training && p->norm_obs;
+    m.upd_ret = p->training != 0;
+    m.gamma = p->gamma;
+    m.returns = returns;
+    m.stats = stats;
+    m.part = (double*)scratch;   // [kPart][kVnMaxBlocks] partials, then the old statistics and the shifts
+    return m;
+}
 
 // Sum of v[0..NV) over the block into out[0..NV) (LDS), NV <= 32: every thread stores
 // its NV values (row stride NV + 1), then TPV = 16 (NV <= 16) or 8 threads per value sum
@@ -77,8 +91,16 @@ __device__ __forceinline__ void load_tile(float* tile, const float* obs, int64_t
     __syncthreads();
 }
 
-// The block sum of a workgroup's moments v, stored as its partial (+ workgroup 0: the
-// snapshot of the old statistics and of the shifts).
+// Workgroup 0's snapshot, after the partials: the old statistics and the shifts of the sums
+// (shift_t: column t's, of thread t <= kD), which the merge reads after the kernel boundary.
+__device__ __forceinline__ void store_snapshot(const MomentsArgs& a, int bid, double shift_t) {
+    const int t = threadIdx.x;
+    double* snap = a.part + kVnMaxBlocks * kPart;
+    if (bid == 0 && t < 2 * kD + 4) snap[t] = a.stats[t];
+    if (bid == 0 && t <= kD) snap[2 * kD + 4 + t] = shift_t;
+}
+
+// The block sum of a workgroup's moments v, stored as its partial (+ the snapshot).
 __device__ __forceinline__ void store_partial(const MomentsArgs& a, int bid, const double* v, const double* sft,
                                              int64_t rows) {
     __shared__ double sh[kVnThreads * (kPart + 1)];
@@ -88,9 +110,7 @@ __device__ __forceinline__ void store_partial(const MomentsArgs& a, int bid, con
     double* part = a.part + bid;
     if (t < kPart - 1) part[(1 + t) * kVnMaxBlocks] = ssum[t];
     if (t == 0) part[0] = (double)rows;
-    double* snap = a.part + kVnMaxBlocks * kPart;
-    if (bid == 0 && t < 2 * kD + 4) snap[t] = a.stats[t];
-    if (bid == 0 && t <= kD) snap[2 * kD + 4 + t] = sft[t];
+    store_snapshot(a, bid, sft[t <= kD ? t : 0]);
 }
 
 // The moments of workgroup `bid`'s rows (blockDim.x == kVnThreads).
@@ -190,162 +210,7 @@ __device__ __forceinline__ void moments_from_rows(const MomentsArgs& a, int bid,
         a.part[(1 + w * (kD + 1) + c) * kVnMaxBlocks + bid] = x;
     }
     if (t == 0) a.part[bid] = (double)rows;
-    double* snap = a.part + kVnMaxBlocks * kPart;
-    if (bid == 0 && t < 2 * kD + 4) snap[t] = a.stats[t];
-    if (bid == 0 && t <= kD) snap[2 * kD + 4 + t] = col_shift;   // thread t <= kD: column t
-}
-
-// ------------------------------------------------------------------ eval: the whole step fused
-// VecNormalize.step_wait with the statistics frozen (training=False, train_ppo_v2.py:450-453):
-// no moments, so nothing crosses workgroups and he_step's own launch can finish the step
-// (step1_vne_kernel, he_vecnorm_attach_eval) -- the obs rows normalized from the step's LDS
-// staging tile, the reward from the thread's register (f32 for VecNormalize, the f64 one for
-// Monitor, which sums the env's own rewards: train_ppo_v2.py:119), returns[done] = 0, Monitor's sums and
-// the normalized terminal obs of done rows.  The same per-element arithmetic as vecnorm.hip's
-// apply (ColNorm, norm_elem): the same bits as he_step + he_vecnorm_apply.
-struct ColNorm {
-    float mh, mls, sh, sl;   // mean = mh + ml, s = 1 / sqrt(var + eps) = sh + sl, mls = RN(ml s)
-};
-__device__ __forceinline__ ColNorm col_norm(double mean, double var, double eps) {
-    const double s = 1.0 / sqrt(var + eps);
-    const float mh = (float)mean, sh = (float)s;
-    // s past FLT_MAX (var + eps = 0, e.g. epsilon = 0 on a constant column): the split terms
-    // would be inf - inf and 0 * inf = NaN for every element; with them 0 an element is
-    // (x - mh) * inf = +-inf -> +-clip, as the f64 (x - mean) / sqrt(var + eps) clips (0 / 0
-    // stays NaN, as in SB3)
-    if (!(sh <= 3.402823466e38f)) return ColNorm{mh, 0.0f, sh, 0.0f};
-    return ColNorm{mh, (float)((mean - (double)mh) * s), sh, (float)(s - (double)sh)};
-}
-// VecNormalize.normalize_obs of one element in f32 from the merged f64 statistics, converted
-// once per column (col_norm): y = (x - mh) (sh + sl) - ml s.  x - mh is exact within a factor
-// 2 of the mean (Sterbenz), else one rounding; the two FMAs round once more (the sl and ml s
-// terms are corrections far below y's last bit).  About 1 f32 ulp of y against the f64
-// (x - mean) / sqrt(var + eps) -- the tests allow 2e-6 absolute at |y| <= clip = 10, ~2 ulp.
-// np.clip in f32 (NaN stays NaN).
-__device__ __forceinline__ float norm_elem(float x, const ColNorm& n, float clip) {
-    const float d = x - n.mh;
-    const float r = fmaf(d, n.sh, fmaf(d, n.sl, -n.mls));
-    return r < -clip ? -clip : (r > clip ? clip : r);
-}
-__device__ __forceinline__ double clip_d(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
-struct ApplyArgs {
-    int32_t norm_obs, norm_reward;
-    int32_t sb3;          // moments = HE_VN_MOMENTS_SB3: the f64 normalization of vn_sb3.h
-    double clip_obs, clip_rew, eps;
-    const double* stats;
-    double* returns;
-    float* obs_out;
-    float* rew_out;
-    float* tobs_out;
-    double* ep_ret;       // Monitor sums (NULL: none)
-    int32_t* ep_len;
-    double* ep_ret_done;
-    int32_t* ep_len_done;
-};
-// What a thread of the fused kernel loads before its step (off the epilogue's path): thread
-// t < kD the statistics of obs column t, thread kD the returns' variance; its row's Monitor sums.
-struct FrozenPre {
-    double m, v, er;
-    int32_t el;
-};
-__device__ __forceinline__ FrozenPre load_frozen(const ApplyArgs& a, int64_t r, bool live) {
-    const int t = threadIdx.x;
-    FrozenPre f{0.0, 1.0, 0.0, 0};
-    if (t < kD) {
-        f.m = a.stats[t];
-        f.v = a.stats[kD + t];
-    } else if (t == kD) {
-        f.v = a.stats[2 * kD + 2];
-    }
-    if (a.ep_ret && live) {
-        f.er = a.ep_ret[r];
-        f.el = a.ep_len[r];
-    }
-    return f;
-}
-// The per-column constants in LDS, made before the step (their f64 square roots and divisions
-// overlap the step's loads; the step's own barrier publishes them).
-struct FrozenNorm {
-    ColNorm cn[kD];
-    double rinv;
-    double m[kD], sd[kD], rsd;   // a.sb3: the columns' mean and sqrt(var + eps), the returns' sqrt(var + eps)
-};
-__device__ __forceinline__ void prep_frozen(FrozenNorm& z, const ApplyArgs& a, const FrozenPre& f) {
-    const int t = threadIdx.x;
-    if (a.sb3) {   // uniform
-        if (t < kD) {
-            z.m[t] = f.m;
-            z.sd[t] = sb3::norm_sd(f.v, a.eps);
-        }
-        if (t == kD) z.rsd = sb3::norm_sd(f.v, a.eps);
-        return;
-    }
-    if (t < kD) z.cn[t] = col_norm(f.m, f.v, a.eps);
-    if (t == kD) z.rinv = 1.0 / sqrt(f.v + a.eps);
-}
-// rows [r0, r0 + rows) of the workgroup, obs staged at tile (row t at tile + t kD), after a
-// workgroup barrier that follows prep_frozen; thread t < rows owns row r0 + t: its reward, done
-// flag and terminal obs row.
-__device__ __forceinline__ void apply_frozen_rows(const ApplyArgs& a, const FrozenNorm& z, int64_t r0, int rows,
-                                                  const float* tile, const FrozenPre& f, float rew, double rew64,
-                                                  bool done, const float* tobs) {
-    const ColNorm* cn = z.cn;
-    const double rinv = z.rinv;
-    const int t = threadIdx.x;
-    const float clip = (float)a.clip_obs;
-    // the obs as a flat coalesced copy: element k = t + 256 q is column k % 13 (rows start at a
-    // row boundary), stepped by 256 % 13 = 9 per q without a division
-    float* dst = a.obs_out + r0 * kD;
-    const int nf = rows * kD;
-    int c = t % kD;
-    const bool sb3n = a.sb3 && a.norm_obs;   // uniform: SB3's f64 (x - mean) / sqrt(var + eps)
-    if (sb3n) {
-#pragma unroll 1
-        for (int k = t; k < nf; k += kVnThreads) {
-            dst[k] = sb3::norm_obs(tile[k], z.m[c], z.sd[c], a.clip_obs);
-            c += kVnThreads % kD;
-            c = c >= kD ? c - kD : c;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < kD; ++q) {
-            const int k = t + q * kVnThreads;
-            if (k < nf) dst[k] = a.norm_obs ? norm_elem(tile[k], cn[c], clip) : tile[k];
-            c += kVnThreads % kD;
-            c = c >= kD ? c - kD : c;
-        }
-    }
-    if (t >= rows) return;
-    const int64_t r = r0 + t;
-    if (a.sb3)
-        a.rew_out[r] = a.norm_reward ? sb3::norm_rew(rew, z.rsd, a.clip_rew) : rew;
-    else
-        a.rew_out[r] = a.norm_reward ? (float)clip_d((double)rew * rinv, -a.clip_rew, a.clip_rew) : rew;
-    if (done && tobs && a.tobs_out) {   // rare: per-row accesses (this thread stored the row)
-        if (sb3n) {
-#pragma unroll 1
-            for (int k = 0; k < kD; ++k)
-                a.tobs_out[r * kD + k] = sb3::norm_obs(tobs[r * kD + k], z.m[k], z.sd[k], a.clip_obs);
-        } else {
-#pragma unroll
-            for (int k = 0; k < kD; ++k) {
-                const float x = tobs[r * kD + k];
-                a.tobs_out[r * kD + k] = a.norm_obs ? norm_elem(x, cn[k], clip) : x;
-            }
-        }
-    }
-    if (done) a.returns[r] = 0.0;   // self.returns[dones] = 0
-    if (a.ep_ret) {                 // Monitor: sum(rewards) of the env's f64 rewards, len(rewards)
-        const double er = f.er + rew64;
-        const int32_t el = f.el + 1;
-        if (done) {
-            a.ep_ret_done[r] = er;
-            a.ep_len_done[r] = el;
-        }
-        a.ep_ret[r] = done ? 0.0 : er;
-        a.ep_len[r] = done ? 0 : el;
-    }
+    store_snapshot(a, bid, col_shift);   // thread t <= kD: column t
 }
 
 }  // namespace vn

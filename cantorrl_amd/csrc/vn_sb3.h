@@ -2,7 +2,7 @@
 // over NumPy, operation for operation, so that the device reproduces the bits of the
 // reference's own stack (train_ppo_v2.py:204,305,450-453; oracle/vecnorm_oracle.py with
 // moments="sb3").  __host__ __device__: vn_sb3_kernel (vecnorm.hip), the eval arm fused into
-// he_step (vn_moments.h apply_frozen_rows) and the host mirror he_host_vecnorm_sb3 run the same
+// he_step (vn_apply.h apply_frozen_rows) and the host mirror he_host_vecnorm_sb3 run the same
 // functions.  The build keeps -ffp-contract=off and correctly rounded f32 divide / sqrt.
 //
 //   obs batch moments   np.mean / np.var over axis 0 of the [n][13] f32 batch: per column one
@@ -13,6 +13,8 @@
 //                       times the count is an f32 product (batch_m2_obs);
 //   normalization       f64 subtract, sqrt and divide, clipped, then rounded to f32 (norm_obs,
 //                       norm_rew) -- no reciprocal.
+// rms_update and clipd are also the default mode's (vecnorm.hip vn_apply_kernel, vn_apply.h
+// SplitNorm): one copy of each.  vn_apply.h wraps norm_obs / norm_rew as the normaliser Sb3Norm.
 #pragma once
 
 #include <hip/hip_runtime.h>
