@@ -9,8 +9,9 @@ kernel pointers into it; step_wait copies the obs / reward / terminated prefix t
 DMA, and freezing an InfoView is one device copy of the info part.  The small-N host path's mapped
 block (he_host_alloc) is the same layout followed by the actions [N, 2], the terminal obs [N, 13]
 and the step's completion flag (one u32), each 256-B aligned.  DeviceVecNormalize's output buffer
-[obs | reward] is the layout's first `terminated` bytes.  Every offset below is in bytes from the
-start of the buffer.
+[obs | reward] is the layout's first `terminated` bytes; its own mapped block (host_io) is that
+head followed by the normalized terminal obs and the finished episodes' Monitor sums (vn_*).
+Every offset below is in bytes from the start of its buffer.
 """
 import numpy as np
 
@@ -46,6 +47,13 @@ class IoLayout:
         self.terminal_obs = _align(self.actions + n * 2 * 4)
         self.flag = _align(self.terminal_obs + n * D * 4)   # the step's completion flag (he_step_signal)
         self.host_total = self.flag + 4
+        # DeviceVecNormalize's host-mapped block (host_io): [obs | reward] as its device buffer,
+        # then the normalized terminal obs [N, 13] and the finished episodes' Monitor return
+        # (f64 [N]) and length (i32 [N])
+        self.vn_terminal_obs = _align(self.terminated)
+        self.vn_ep_ret_done = _align(self.vn_terminal_obs + n * D * 4)
+        self.vn_ep_len_done = _align(self.vn_ep_ret_done + n * 8)
+        self.vn_host_total = self.vn_ep_len_done + n * 4
         self._info = [(k, dt, o - self.info0, o - self.info0 + b) for k, (dt, o, b) in self.fields.items()]
 
     def obs_reward(self, h):

@@ -130,6 +130,7 @@ class HeVecnormParams(ctypes.Structure):
 
 HE_VN_MOMENTS_F64, HE_VN_MOMENTS_SB3 = range(2)
 HE_VN_SB3_MAX_ENVS = 4096
+HE_VN_STEP_MAX_ENVS = 256   # he_vecnorm_attach_step: one step workgroup
 VN_MOMENTS = {"f64": HE_VN_MOMENTS_F64, "sb3": HE_VN_MOMENTS_SB3}
 
 
@@ -177,6 +178,7 @@ SIG = {
     "he_vecnorm_apply": (_i32, [_vnp, _i64] + [_vp] * 15 + [_vp]),
     "he_vecnorm_attach": (_i32, [_vp, _vnp, _vp, _vp, _vp]),
     "he_vecnorm_attach_eval": (_i32, [_vp, _vnp, ctypes.POINTER(HeVecnormOut)]),
+    "he_vecnorm_attach_step": (_i32, [_vp, _vnp, ctypes.POINTER(HeVecnormOut), _vp]),
     "he_vecnorm_reset": (_i32, [_vnp, _i64] + [_vp] * 5 + [_vp]),
     "he_host_vecnorm_sb3": (_i32, [_vnp, _i64] + [_vp] * 9),
     "he_fixed_european_marks": (_i32, [_vp, _i64, _i32, ctypes.c_double, _vp, _vp, _vp, _vp]),

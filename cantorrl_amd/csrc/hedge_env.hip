@@ -36,6 +36,7 @@
 
 #include "vn_apply.h"
 #include "vn_moments.h"
+#include "vn_step.h"
 #include <string>
 #include <vector>
 
@@ -1506,6 +1507,7 @@ struct VnHook {
     float rew;
     double rew64;   // the f64 reward (Monitor's sums)
     bool term;
+    float* trow;    // in: where a done env's terminal obs row is kept as well (LDS; NULL: io.tobs alone)
 };
 
 // he_step_signal: the end of an he_step launch, raised in host-mapped memory so the host can
@@ -1767,6 +1769,10 @@ __device__ __forceinline__ void step_body(const Params& pk, int64_t n_envs, cons
                 if (io.tobs) {
 #pragma unroll
                     for (int c = 0; c < kObs; ++c) io.tobs[i * kObs + c] = orow[c];
+                }
+                if (hook && hook->trow) {
+#pragma unroll
+                    for (int c = 0; c < kObs; ++c) hook->trow[c] = orow[c];
                 }
                 env_reset_common(p, e);
                 if (REPLAY) {
@@ -2033,6 +2039,43 @@ __global__ __launch_bounds__(kBlock) void step1_vne_kernel(const Params* __restr
     const int rows = (int)((n - r0) < kEpb ? n - r0 : kEpb);
     __syncthreads();  // the workgroup's obs rows (LDS, the final ones incl. reset obs) and fz visible to all
     vn::apply_frozen_rows(va, fz, r0, rows, hk.tile, fp, hk.rew, hk.rew64, hk.term, sio.tobs);
+}
+
+// he_step with the whole VecNormalize step attached (he_vecnorm_attach_step): n <= kEpb envs
+// are ONE step workgroup, so nothing of the step crosses workgroups in either moments mode,
+// training or frozen -- step_body (with or without the info fields), a barrier, then
+// vn::step_rows over the workgroup's rows from the LDS obs tile and the thread's registers
+// (reward, f64 reward, done flag), with no read back of what the step stored: a done row's
+// terminal obs stays in a second LDS tile (VnHook::trow).  The step's signal (he_step_signal)
+// is raised here, after the VecNormalize stores, on every path: the host-mapped route of
+// DeviceVecNormalize.step_wait is this one launch and the wait for that word.
+// Mode and training are uniform runtime branches (vn::StepArgs).  The step itself is the one the
+// unarmed he_step would launch -- FAST without info fields in the FAST configuration, never with
+// them -- and the f64 training sums take the order of the route he_vecnorm_attach would take on
+// that step (vn::SumOrder), so an armed step has the bits of the separate launches either way.
+template <int MODE, bool INFO, bool BOOK, bool FAST, bool GS>
+__global__ __launch_bounds__(kBlock) void step1_vnw_kernel(const Params* __restrict__ pc, int64_t n, const float4* tA,
+                                                           const float4* tB, const double* tC, State s, Io io,
+                                                           int slot0, vn::StepArgs vw) {
+    static_assert(kEpw == 64 && kEpb == kBlock && kEpb == vn::kVnChunk, "one env per thread, one workgroup");
+    static_assert(!(INFO && FAST), "the info kernels are never FAST");
+    constexpr vn::SumOrder ORDER = INFO ? vn::kBlock : vn::kColumns;
+    uint32_t* const sig = io.sig;
+    io.sig = nullptr;   // more work follows the step in the launch
+    __shared__ vn::StepShared sh;
+    __shared__ float ttile[kEpb * kObs];
+    const int t = threadIdx.x;
+    const int rows = (int)(n < kEpb ? n : kEpb);   // the launch is one workgroup: rows [0, n)
+    const vn::StepPre pre = vn::load_step<ORDER>(vw, t < rows);
+    vn::prep_step(vw, sh, pre);
+    VnHook hk{nullptr, 0.0f, 0.0, false, ttile + t * kObs};
+    step_body<MODE, INFO, true, BOOK, FAST, false, GS>(*pc, n, tA, tB, tC, s, io, 1, slot0, 0, &hk);
+    __syncthreads();  // the workgroup's obs rows (LDS, the final ones incl. reset obs), the terminal rows and sh.z
+    vn::step_rows<ORDER>(vw, sh, pre, rows, hk.tile, ttile, hk.rew, hk.rew64, hk.term);
+    if (sig) {
+        io.sig = sig;
+        raise_step_signal(io);
+    }
 }
 
 // The same moments after any other he_step launch (info requested, a fused market block).
@@ -4132,6 +4175,8 @@ struct he_env {
     bool vne_on = false;         // he_vecnorm_attach_eval: he_step also runs the eval VecNormalize step
     vn::ApplyArgs vne{};
     he_vecnorm_params vne_p{};
+    bool vnw_on = false;         // he_vecnorm_attach_step: he_step runs the whole VecNormalize step (step1_vnw_kernel)
+    vn::StepArgs vnw{};
     BookOpt* dbook = nullptr;   // liability book, device copy (generate modes)
     double* dbook_tab = nullptr;  // book tau table (book_option)
     int64_t* d_eps = nullptr;     // he_reset_episodes: the host-drawn episode rows, staged
@@ -4486,11 +4531,22 @@ static void launch_step(he_env* env, const Params& p, const Io& io, bool info, i
         return;
     }
     const bool single = k == 1 && !io.sums;  // he_step (rollouts keep the episode summaries)
+    constexpr bool REPLAY = (MODE == HE_MODE_REPLAY);
+    const Params* pc = env->dparams + (REPLAY ? 0 : env->cur_buf);
+    const float4* tA = REPLAY ? p.rec : p.tileA;
+    const float4* tB = REPLAY ? p.recg : p.tileB;
+    if (single && env->vnw_on) {  // + the whole VecNormalize step, one workgroup (he_vecnorm_attach_step: never a book)
+        if constexpr (!BOOK) {
+            pick([&](auto info_c) {
+                constexpr bool INFO = decltype(info_c)::value;
+                launch_timed(env, step1_vnw_kernel<MODE, INFO, false, FAST && !INFO, GS>, grid, block, st, pc, p.n, tA,
+                             tB, p.tileC, env->s, io, slot0, env->vnw);
+            }, info);
+            env->vn_fused = true;
+            return;
+        }
+    }
     if (single && !info) {
-        constexpr bool REPLAY = (MODE == HE_MODE_REPLAY);
-        const Params* pc = env->dparams + (REPLAY ? 0 : env->cur_buf);
-        const float4* tA = REPLAY ? p.rec : p.tileA;
-        const float4* tB = REPLAY ? p.recg : p.tileB;
         StepIo sio{io.act, io.obs, io.rew, io.term, io.trunc, io.tobs, io.sig, io.sig_cnt, io.sig_seq};
         if (env->vne_on && io.obs && io.rew && io.term && io.tobs) {  // + the eval VecNormalize step
             launch_timed(env, step1_vne_kernel<MODE, BOOK, FAST, GS>, grid, block, st, pc, p.n, tA, tB, p.tileC, env->s,
@@ -5286,7 +5342,12 @@ he_status he_step(he_env* env, const float* actions, float* obs, float* reward, 
     }
     // he_vecnorm_attach arms THIS step only (one-shot): steps nobody armed -- the inner env
     // stepped directly, another wrapper's -- never touch a wrapper's returns or partials
-    const bool vn = env->vn_on, vne = env->vne_on;
+    const bool vn = env->vn_on, vne = env->vne_on, vnw = env->vnw_on;
+    if (vnw && (!obs || !reward || !terminated || !terminal_obs)) {
+        env->vn_on = env->vne_on = env->vnw_on = false;
+        return fail(env, HE_EINVAL, "he_vecnorm_attach_step: he_step needs the obs, reward, terminated and terminal_obs "
+                                    "buffers");
+    }
     if ((vn || vne) && (!obs || !reward)) {
         env->vn_on = env->vne_on = false;
         return fail(env, HE_EINVAL, "he_vecnorm_attach: he_step needs the obs and reward buffers");
@@ -5314,7 +5375,8 @@ he_status he_step(he_env* env, const float* actions, float* obs, float* reward, 
     env->vn_fused = false;
     he_status s = launch_steps(env, io, want_info, 1, stream);
     if (sig && s == HE_OK) env->sig_seq = io.sig_seq;
-    env->vn_on = env->vne_on = false;
+    env->vn_on = env->vne_on = env->vnw_on = false;
+    if (vnw) return s;   // he_vecnorm_attach_step: the launch made the whole VecNormalize step
     if (s == HE_OK && vne && !env->vn_fused) {
         // another step kernel ran (info requested): the eval VecNormalize step as its own
         // launch.  he_vecnorm_step with training = 0 launches the apply kernel alone, which reads
@@ -5362,6 +5424,7 @@ he_status he_vecnorm_attach(he_env* env, const he_vecnorm_params* p, double* ret
     m.shift_mean = 1;
     env->vn = m;
     env->vn_on = m.upd_obs || m.upd_ret;
+    env->vnw_on = false;
     return HE_OK;
 }
 
@@ -5387,7 +5450,48 @@ he_status he_vecnorm_attach_eval(he_env* env, const he_vecnorm_params* p, const 
     env->vne = vn::apply_args(p, *out);
     env->vne_p = *p;
     env->vne_on = true;
-    env->vn_on = false;
+    env->vn_on = env->vnw_on = false;
+    return HE_OK;
+}
+
+he_status he_vecnorm_attach_step(he_env* env, const he_vecnorm_params* p, const he_vecnorm_out* out, void* scratch) {
+    if (!env) return HE_EINVAL;
+    (void)scratch;   // one workgroup holds the batch: no partials
+    if (!p) {  // disarm
+        env->vnw_on = false;
+        return HE_OK;
+    }
+    if (p->obs_dim != kObs || !isfinite(p->gamma) || !(p->clip_obs >= 0.0) || !(p->clip_reward >= 0.0) ||
+        !(p->epsilon >= 0.0))
+        return fail(env, HE_EINVAL, "bad he_vecnorm_params");
+    if (p->moments != HE_VN_MOMENTS_F64 && p->moments != HE_VN_MOMENTS_SB3)
+        return fail(env, HE_EINVAL, "bad he_vecnorm_params (moments)");
+    if (kEpb != HE_VN_STEP_MAX_ENVS)
+        return fail(env, HE_EINVAL, "he_vecnorm_attach_step needs %d envs per step workgroup", HE_VN_STEP_MAX_ENVS);
+    if (env->cfg.n_envs > HE_VN_STEP_MAX_ENVS)
+        return fail(env, HE_EINVAL, "he_vecnorm_attach_step covers up to %d envs, one step workgroup (this handle has "
+                                    "%lld: use he_vecnorm_attach / he_vecnorm_step)",
+                    HE_VN_STEP_MAX_ENVS, (long long)env->cfg.n_envs);
+    if (env->cfg.book_size > 0)
+        return fail(env, HE_EINVAL, "he_vecnorm_attach_step: no kernel for a liability book (use he_vecnorm_attach / "
+                                    "he_vecnorm_step)");
+    if (!env->cfg.autoreset)   // the step keeps a done row's terminal obs where it resets the row
+        return fail(env, HE_EINVAL, "he_vecnorm_attach_step needs autoreset = 1 (use he_vecnorm_attach / "
+                                    "he_vecnorm_step)");
+    if (!out || !out->stats || !out->returns || !out->obs_out || !out->reward_out)
+        return fail(env, HE_EINVAL, "he_vecnorm_out: stats / returns / obs_out / reward_out are NULL");
+    if ((out->ep_return != nullptr) != (out->ep_length != nullptr) ||
+        (out->ep_return && (!out->ep_return_done || !out->ep_length_done)))
+        return fail(env, HE_EINVAL, "he_vecnorm_out: the Monitor buffers come together");
+    vn::StepArgs w = {};
+    w.m = vn::moments_args(p, env->cfg.n_envs, out->returns, const_cast<double*>(out->stats), nullptr);
+    w.m.rows_per_block = kEpb;
+    w.m.shift_mean = 1;
+    w.a = vn::apply_args(p, *out);
+    w.training = p->training != 0;
+    env->vnw = w;
+    env->vnw_on = true;
+    env->vn_on = env->vne_on = false;
     return HE_OK;
 }
 

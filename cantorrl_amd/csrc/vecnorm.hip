@@ -27,7 +27,9 @@
 // This file holds the kernels, their argument block and the C entry points.  What the kernels
 // share with the epilogues fused into he_step (hedge_env.hip) and with the host mirror is in the
 // headers: the moments and the snapshot in vn_moments.h; the normalisers, the flat obs pass, a
-// row's tail and ApplyArgs in vn_apply.h; SB3's arithmetic, clipd and rms_update in vn_sb3.h.
+// row's tail and ApplyArgs in vn_apply.h; SB3's arithmetic, clipd and rms_update in vn_sb3.h; the
+// workgroup-wide parts of vn_sb3_kernel, and the whole step of <= 256 envs inside he_step's own
+// launch (he_vecnorm_attach_step), in vn_step.h.
 
 #include <hip/hip_runtime.h>
 
@@ -40,6 +42,7 @@
 #include "vn_apply.h"
 #include "vn_moments.h"
 #include "vn_sb3.h"
+#include "vn_step.h"
 
 namespace {
 
@@ -157,14 +160,13 @@ __global__ void __launch_bounds__(kVnThreads) vn_apply_kernel(VnArgs a) {
             const double n_a = ssum[0], s1 = ssum[1 + c], s2 = ssum[2 + kD + c];
             // np.mean / np.var(ddof=0) of the batch from the shifted sums, then
             // RunningMeanStd.update_from_moments
-            const double mean_a = old[2 * kD + 4 + c] + s1 / n_a;
-            const double m2 = s2 - s1 * (s1 / n_a);
-            const double var_a = (m2 > 0.0 ? m2 : 0.0) / n_a;
+            double mean_a, m_b;
+            vn::batch_from_sums(old[2 * kD + 4 + c], n_a, s1, s2, &mean_a, &m_b);
             const int im = (c < kD) ? c : 2 * kD + 1, iv = (c < kD) ? kD + c : 2 * kD + 2;
             double mean = old[im], var = old[iv];
             if ((c < kD && a.m.upd_obs) || (c == kD && a.m.upd_ret)) {
                 double count = (c < kD) ? old[2 * kD] : old[2 * kD + 3];
-                sb3::rms_update(&mean, &var, &count, mean_a, var_a * n_a, n_a);
+                sb3::rms_update(&mean, &var, &count, mean_a, m_b, n_a);
                 if (blockIdx.x == 0) {
                     if (c == 0) a.m.stats[2 * kD] = count;
                     if (c == kD) a.m.stats[2 * kD + 3] = count;
@@ -256,16 +258,7 @@ __global__ void __launch_bounds__(kVnThreads) vn_sb3_kernel(VnArgs a) {
     RowIn pin = {};
     if (!a.reset && t < n) pin = row_in(a, t);
     double ret0 = upd_ret && t < n ? a.m.returns[t] : 0.0;
-    double st_mean = 0.0, st_var = 1.0, st_count = 0.0;   // lanes 0 .. 12 an obs column, lane 13 the returns
-    if (t < kD) {
-        st_mean = a.m.stats[t];
-        st_var = a.m.stats[kD + t];
-        st_count = a.m.stats[2 * kD];
-    } else if (t == kD) {
-        st_mean = a.m.stats[2 * kD + 1];
-        st_var = a.m.stats[2 * kD + 2];
-        st_count = a.m.stats[2 * kD + 3];
-    }
+    const vn::StatLane st = vn::load_stat_lane(a.m.stats);   // lanes 0 .. 12 an obs column, lane 13 the returns
     if (upd_ret) {
         for (int r = t; r < n; r += kVnThreads) {
             const double ret = r == t ? sb3::ret_update(ret0, a.m.gamma, pin.rw)
@@ -273,26 +266,7 @@ __global__ void __launch_bounds__(kVnThreads) vn_sb3_kernel(VnArgs a) {
             a.m.returns[r] = ret;
             rbuf[r] = ret;
         }
-        // thread t is node t of the pairwise tree: a leaf, a split or (most) nothing
-        const int levels = sb3::pw_levels(n);
-        const sb3::Node nd = t >= 1 && t < (2 << levels) ? sb3::pw_node(n, t) : sb3::Node{0, 0};
-        __syncthreads();
-        for (int pass = 0; pass < 2; ++pass) {
-            if (nd.n > 0 && nd.n <= sb3::kLeafMax) nval[t] = sb3::pw_leaf(rbuf + nd.lo, nd.n);
-            __syncthreads();
-            for (int d = levels - 1; d >= 0; --d) {   // the splits of level d, their halves done
-                if (nd.n > sb3::kLeafMax && (t >> d) == 1) nval[t] = nval[2 * t] + nval[2 * t + 1];
-                __syncthreads();
-            }
-            bret[pass] = nval[1] / (double)n;
-            if (pass == 0) {
-                for (int r = t; r < n; r += kVnThreads) {
-                    const double d = rbuf[r] - bret[0];
-                    rbuf[r] = d * d;
-                }
-                __syncthreads();   // also: every thread has read nval[1] before the second pass writes it
-            }
-        }
+        vn::sb3_returns_moments(n, rbuf, nval, bret);
     }
     float bmean = 0.0f, bvar = 0.0f;   // lanes 0 .. 12: np.mean / np.var of their obs column
     if (a.m.upd_obs) {
@@ -318,24 +292,7 @@ __global__ void __launch_bounds__(kVnThreads) vn_sb3_kernel(VnArgs a) {
         bvar = v / (float)n;
     }
     // the 14 statistics: RunningMeanStd.update_from_moments, stored, and the columns' constants
-    if (t < kD) {
-        if (a.m.upd_obs) {
-            sb3::rms_update(&st_mean, &st_var, &st_count, (double)bmean, sb3::batch_m2_obs(bvar, n), (double)n);
-            a.m.stats[t] = st_mean;
-            a.m.stats[kD + t] = st_var;
-            if (t == 0) a.m.stats[2 * kD] = st_count;
-        }
-        smean[t] = st_mean;
-        ssd[t] = sb3::norm_sd(st_var, a.a.eps);
-    } else if (t == kD) {
-        if (upd_ret) {
-            sb3::rms_update(&st_mean, &st_var, &st_count, bret[0], bret[1] * (double)n, (double)n);
-            a.m.stats[2 * kD + 1] = st_mean;
-            a.m.stats[2 * kD + 2] = st_var;
-            a.m.stats[2 * kD + 3] = st_count;
-        }
-        srsd = sb3::norm_sd(st_var, a.a.eps);
-    }
+    vn::sb3_update_stats(st, a.m.upd_obs != 0, upd_ret, bmean, bvar, bret, n, a.m.stats, a.a.eps, smean, ssd, &srsd);
     __syncthreads();
     const vn::Sb3Norm nz{smean, ssd, &srsd, a.a.clip_obs, a.a.clip_rew};
     if (tile_all) {   // the thread's elements are still in its registers

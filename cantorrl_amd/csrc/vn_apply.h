@@ -4,6 +4,8 @@
 //   vn_apply_kernel, vn_sb3_kernel (vecnorm.hip)   the separate launches;
 //   apply_frozen_rows (below)                      the eval step fused into he_step
 //                                                  (hedge_env.hip step1_vne_kernel);
+//   step_rows (vn_step.h)                          the whole step of <= 256 envs fused into
+//                                                  he_step (hedge_env.hip step1_vnw_kernel);
 //   he_host_vecnorm_sb3 (vecnorm.hip)              the host mirror, no Monitor.
 // The pieces: the two normalisers (SplitNorm: moments = f64, the f32 split of the f64
 // statistics; Sb3Norm: moments = sb3, SB3's own f64 arithmetic of vn_sb3.h), the flat coalesced

@@ -9,7 +9,9 @@
 // running returns, stored as partial [kPart][kVnMaxBlocks] (count, S1[D + 1], S2[D + 1]);
 // workgroup 0 also stores a snapshot of the old statistics and the shifts (store_snapshot),
 // which vn_apply_kernel (vecnorm.hip) reads after the kernel boundary.  The second half of the
-// step -- normalisers, obs pass, a row's tail, the fused eval step -- is vn_apply.h.
+// step -- normalisers, obs pass, a row's tail, the fused eval step -- is vn_apply.h; the whole
+// step by one workgroup (vn_step.h) takes the same sums from rows in LDS
+// (moments_rows_block_order) and the batch moments from them as the merge does (batch_from_sums).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -79,6 +81,55 @@ __device__ __forceinline__ void block_sum(const double* v, double* buf, double* 
         if (j == 0) out[c] = x;
     }
     __syncthreads();
+}
+
+// moments_body's partial of ONE workgroup whose rows are already in LDS (obs row r at
+// tile + r * kD, the updated running returns in rbuf), bit for bit, without block_sum's 59 KB
+// buffer: value c of v[] (S1 then S2, column c % (kD + 1), the returns last) is summed by the
+// same 8 threads over the same rows in the same order -- thread (c, j) the rows j, j + 8, ...,
+// then the butterfly over its 8-lane group -- each row's term made from the tile where
+// block_sum reads it back.  A row past `rows`, or a value that is not updated, adds the 0.0
+// moments_body leaves there.  shift: this thread's column's (load_block_shift).  The sums land
+// in ssum[0 .. kPart - 1) in v[]'s order (LDS; the caller barriers before reading them).
+constexpr int kBlockTpv = 8;   // block_sum<kPart - 1>'s threads per value
+__device__ __forceinline__ double load_block_shift(const MomentsArgs& a) {
+    const int c = (int)(threadIdx.x / kBlockTpv) % (kD + 1);
+    return a.stats[c < kD ? c : 2 * kD + 1];
+}
+__device__ __forceinline__ void moments_rows_block_order(const MomentsArgs& a, const float* tile, const double* rbuf,
+                                                         int rows, double shift, double* ssum) {
+    static_assert((kPart - 1) * kBlockTpv <= kVnThreads && kPart - 1 > 16, "block_sum<kPart - 1>: 8 threads per value");
+    const int t = threadIdx.x;
+    if (t >= (kPart - 1) * kBlockTpv) return;
+    const int c = t / kBlockTpv, j = t % kBlockTpv;
+    const int col = c % (kD + 1);
+    const bool sq = c > kD;
+    const bool on = col < kD ? a.upd_obs != 0 : a.upd_ret != 0;
+    double x = 0.0;
+#pragma unroll 4
+    for (int k = 0; k < kVnThreads / kBlockTpv; ++k) {
+        const int r = j + kBlockTpv * k;
+        double term = 0.0;
+        if (on && r < rows) {
+            const double d = (col < kD ? (double)tile[r * kD + col] : rbuf[r]) - shift;
+            term = sq ? d * d : d;
+        }
+        x += term;
+    }
+#pragma unroll
+    for (int m = kBlockTpv / 2; m >= 1; m >>= 1) x += __shfl_xor(x, m, kBlockTpv);
+    if (j == 0) ssum[c] = x;
+}
+
+// np.mean and np.var(ddof=0) * n of a batch of n_a values from their shifted sums
+// s1 = sum d, s2 = sum d^2, d = x - shift: what RunningMeanStd.update_from_moments takes
+// (vn_apply_kernel's merge and the one-workgroup step of vn_step.h).
+__device__ __forceinline__ void batch_from_sums(double shift, double n_a, double s1, double s2, double* mean_a,
+                                                double* m_b) {
+    *mean_a = shift + s1 / n_a;
+    const double m2 = s2 - s1 * (s1 / n_a);
+    const double var_a = (m2 > 0.0 ? m2 : 0.0) / n_a;
+    *m_b = var_a * n_a;
 }
 
 // Rows [c0, c0 + rows) of obs -> LDS tile, as a flat coalesced copy (the [N][13] rows are
@@ -171,8 +222,12 @@ __device__ __forceinline__ double load_col_shift(const MomentsArgs& a) {
 // the statistics agree to rounding, not bit for bit (test_fused_moments_equal_separate_launch).
 constexpr int kColGroups = kVnThreads / (kD + 1);            // 18
 constexpr int kColThreads = kColGroups * (kD + 1);           // 252
-__device__ __forceinline__ void moments_from_rows(const MomentsArgs& a, int bid, const float* tile, float rew,
-                                                  double ret_prev, double col_shift) {
+// moments_rows_to: the sums themselves, handed to sink(v, x) -- value v of the partial
+// (v = w (kD + 1) + c: S1 then S2 of column c) by thread v -- so that the one-workgroup step
+// (vn_step.h) keeps them in LDS where moments_from_rows stores the partial.
+template <class Sink>
+__device__ __forceinline__ int moments_rows_to(const MomentsArgs& a, int bid, const float* tile, float rew,
+                                               double ret_prev, double col_shift, Sink sink) {
     __shared__ double rbuf[kVnThreads];
     __shared__ double red[kColGroups][kD + 1][2];
     const int64_t r0 = (int64_t)bid * a.rows_per_block;
@@ -206,10 +261,16 @@ __device__ __forceinline__ void moments_from_rows(const MomentsArgs& a, int bid,
         double x = 0.0;
 #pragma unroll
         for (int g = 0; g < kColGroups; ++g) x += red[g][c][w];
-        // partial layout: [count, S1[kD + 1], S2[kD + 1]] (S1[kD] / S2[kD]: the returns)
-        a.part[(1 + w * (kD + 1) + c) * kVnMaxBlocks + bid] = x;
+        sink(w * (kD + 1) + c, x);
     }
-    if (t == 0) a.part[bid] = (double)rows;
+    return rows;
+}
+__device__ __forceinline__ void moments_from_rows(const MomentsArgs& a, int bid, const float* tile, float rew,
+                                                  double ret_prev, double col_shift) {
+    // partial layout: [count, S1[kD + 1], S2[kD + 1]] (S1[kD] / S2[kD]: the returns)
+    const int rows = moments_rows_to(a, bid, tile, rew, ret_prev, col_shift,
+                                     [&a, bid](int v, double x) { a.part[(1 + v) * kVnMaxBlocks + bid] = x; });
+    if (threadIdx.x == 0) a.part[bid] = (double)rows;
     store_snapshot(a, bid, col_shift);   // thread t <= kD: column t
 }
 

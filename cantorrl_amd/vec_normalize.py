@@ -14,6 +14,11 @@ leave the GPU on the tensor path (`reset_tensors` / `step_tensors`).
 arithmetic bit for bit instead of the default f64 batch moments (csrc/vn_sb3.h, one
 workgroup per step).
 
+A NumPy wrapper of up to 256 envs steps through host-mapped memory (`host_io`): he_step's own
+launch makes the whole VecNormalize step (he_vecnorm_attach_step, csrc/vn_step.h), writes what
+the host reads into a mapped block and raises the step's completion word -- one launch, no
+DMA, the bits of the device-buffer route.
+
 Statistics are saved with `save(path)` as NPZ (no pickle) and restored with
 `DeviceVecNormalize.load(path, venv)`.
 """
@@ -41,11 +46,17 @@ class _RmsView:
 
 class DeviceVecNormalize:
     def __init__(self, venv, training=True, norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0,
-                 gamma=0.99, epsilon=1e-8, moments="f64"):
+                 gamma=0.99, epsilon=1e-8, moments="f64", host_io="auto"):
         """moments: "f64" (default, any number of envs) takes the batch moments as f64 sums and
         normalizes in f32; "sb3" (up to 4,096 envs) reproduces SB3's NumPy arithmetic bit for bit --
         f32 row-order obs moments, pairwise f64 returns moments, f64 normalization -- in one
-        launch of one workgroup per step (csrc/vn_sb3.h)."""
+        launch of one workgroup per step (csrc/vn_sb3.h).
+
+        host_io: step_wait of up to 256 envs as ONE he_step launch that makes the whole
+        VecNormalize step and writes what the host reads into host-mapped memory
+        (he_vecnorm_attach_step + he_step_signal; the bits of the other route).  "auto": on for a
+        NumPy wrapper over an env that has its host block, check_finite off and
+        CANTORRL_VN_FUSED != "0"; False: never; True: ValueError where it cannot be."""
         if moments not in _lib.VN_MOMENTS:
             raise ValueError(f"moments must be one of {sorted(_lib.VN_MOMENTS)}, not {moments!r}")
         if moments == "sb3" and venv.num_envs > _lib.HE_VN_SB3_MAX_ENVS:
@@ -78,7 +89,8 @@ class DeviceVecNormalize:
         self._ep_len_done = torch.zeros(n, dtype=torch.int32, device=dev)
         # Monitor episode sums kept on the device when the env has Monitor (monitor_keywords):
         # they sum its f64 step rewards (train_ppo_v2.py:119; hedging_env_v2.py:262,294)
-        self._monitor = getattr(venv, "_rew64", None) is not None
+        # (venv._rew64 is only where those come from: an env may expose the column without Monitor)
+        self._monitor = getattr(venv, "monitor_keywords", None) is not None
         self._check(self.lib.he_vecnorm_init(self._p(self._stats), D, self._stream()), "he_vecnorm_init")
         # the moments half of each training step inside the env's he_step launch
         # (he_vecnorm_attach; up to 65,536 envs), then he_vecnorm_apply; else he_vecnorm_step
@@ -87,6 +99,8 @@ class DeviceVecNormalize:
         self._fusable_eval = on   # the eval arm exchanges nothing between workgroups: any n
         self._actions_pending = None
         self._args = None   # _call_args cache
+        self._hout = self._host_route(host_io, on)
+        self._raw_host = False   # the last step's raw obs / reward are in the env's host block
         if self.return_numpy:
             venv._warm_pinned([L.terminated] * 3 + [n] * 3 + [L.reward, 8 * n, 4 * n, venv._info_flat.numel()])
         self._t_start = time.time()
@@ -100,6 +114,36 @@ class DeviceVecNormalize:
     def _check(self, st, what, handle=None):
         """_lib.check; handle: the env's, for the entry points that take it (they leave a message)."""
         _lib.check(self.lib, handle, st, what)
+
+    def _host_route(self, host_io, fused):
+        """The wrapper's host-mapped block (_HostOut) when step_wait takes the one-launch route,
+        else None.  The arm is tried once here, so a configuration the library has no kernel
+        for (a liability book, autoreset off) is settled now: "auto" keeps the other route, True raises."""
+        v, n = self.venv, self.num_envs
+        why = None
+        if not self.return_numpy:
+            why = "the wrapper returns device tensors (return_numpy=False)"
+        elif getattr(v, "_hio", None) is None:
+            why = "the env has no host-mapped block (host_io)"
+        elif n > _lib.HE_VN_STEP_MAX_ENVS:
+            why = f"{n} envs are more than one step workgroup ({_lib.HE_VN_STEP_MAX_ENVS})"
+        elif v.check_finite:
+            why = "check_finite counts on the device after the step"
+        elif not fused:
+            why = 'CANTORRL_VN_FUSED="0"'
+        hout = None
+        if host_io and why is None:
+            hout = _HostOut(self)
+            h = v._h
+            if self.lib.he_vecnorm_attach_step(h, ctypes.byref(self._params()), hout.out_ref, None) != _lib.HE_OK:
+                why = self.lib.he_last_error(h).decode()
+                hout.free()
+                hout = None
+            else:
+                self.lib.he_vecnorm_attach_step(h, None, None, None)
+        if host_io is True and hout is None:
+            raise ValueError(f"host_io=True: {why}")
+        return hout
 
     def _params(self):
         p = _lib.HeVecnormParams()
@@ -189,6 +233,7 @@ class DeviceVecNormalize:
     # ------------------------------------------------------------------ device path
     def reset_tensors(self):
         obs = self.venv.reset_tensors()
+        self._raw_host = False
         self._check(self.lib.he_vecnorm_reset(ctypes.byref(self._params()), self.num_envs, self._p(obs),
                                               self._p(self._returns), self._p(self._stats), self._p(self._scratch),
                                               self._p(self._obs_out), self._stream()), "he_vecnorm_reset")
@@ -230,6 +275,7 @@ class DeviceVecNormalize:
         step's VecNormalize work runs outside he_step's own launch (the fused eval step adds
         it from registers)."""
         c = self._call_args()
+        self._raw_host = False   # this step's raw obs / reward land in the env's device buffers
         fused = self._arm(c)
         if not info and self._monitor and fused != "eval":
             info = True
@@ -273,16 +319,32 @@ class DeviceVecNormalize:
         return True
 
     def close(self):
-        self.venv.close()
+        self.venv.close()   # waits for the device: the last step that wrote the block has completed
+        hout, self._hout = getattr(self, "_hout", None), None
+        if hout is not None:
+            hout.free()
+
+    def __del__(self):
+        try:
+            hout, self._hout = getattr(self, "_hout", None), None
+            if hout is not None:
+                torch.cuda.synchronize(self.device)
+                hout.free()
+        except Exception:
+            pass
 
     @property
     def terminal_obs_tensor(self):
         return self._tobs_out
 
     def get_original_obs(self):
+        if self._raw_host:   # a host-route step: its raw values are in the env's block
+            return self._layout.obs_reward(self.venv._hio.io)[0].copy()
         return self.venv._obs.cpu().numpy()
 
     def get_original_reward(self):
+        if self._raw_host:
+            return self._layout.obs_reward(self.venv._hio.io)[1].copy()
         return self.venv._rew.cpu().numpy()
 
     # ------------------------------------------------------------------ SB3 VecEnv API
@@ -295,6 +357,9 @@ class DeviceVecNormalize:
 
     def step_wait(self):
         actions, self._actions_pending = self._actions_pending, None
+        # (actions already on the device keep the device-buffer route: no copy back to the host)
+        if self._hout is not None and not (isinstance(actions, torch.Tensor) and actions.is_cuda):
+            return self._step_wait_host(actions)
         obs, rew, term, _ = self.step_tensors(actions)
         if not self.return_numpy:
             return obs, rew, term.bool(), InfoView(self.venv, None)
@@ -305,6 +370,39 @@ class DeviceVecNormalize:
         if done.any():
             infos._materialize_done(done)
         return (*self._layout.obs_reward(h), done, infos)
+
+    def _step_wait_host(self, actions):
+        """step_wait as one launch (host_io): the actions go into the env's mapped block, the
+        armed he_step makes the env's step and the whole VecNormalize step (he_vecnorm_attach_step:
+        raw outputs and info fields into the env's block, normalized ones into this object's) and
+        raises the env block's flag word after its last store; the results are copied out once
+        (private arrays: a later step never overwrites them).  No DMA, no event wait."""
+        v, w = self.venv, self._hout
+        z, L = v._hio, self._layout
+        c = self._call_args()
+        np.copyto(z.act, np.asarray(actions, dtype=np.float32).reshape(self.num_envs, 2))
+        v._retire_view()
+        lib, h, stream = self.lib, v._h, self._stream()
+        self._check(lib.he_vecnorm_attach_step(h, c[2], w.out_ref, None), "he_vecnorm_attach_step", h)
+        try:
+            self._check(lib.he_step_signal(h, z.d_flag), "he_step_signal", h)
+            self._check(lib.he_step(h, *z.step_args, stream), "he_step", h)
+        except BaseException:   # the armed he_step did not run: nothing may keep this object's buffers
+            lib.he_vecnorm_attach_step(h, None, None, None)
+            lib.he_step_signal(h, None)
+            raise
+        self._check(lib.he_signal_wait(h, z.h_flag, stream), "he_signal_wait", h)
+        self._raw_host = True
+        obs, rew = L.obs_reward(w.io.copy())
+        eh = z.io.copy()
+        done = eh[L.terminated:L.truncated].view(np.bool_)   # the kernels store 0 / 1
+        infos = _NormInfoView(self, done)
+        infos._host = L.split_info(eh[L.info0:])
+        if done.any():
+            mon = self._monitor
+            infos._ends = _end_episodes(v, done, w.tobs.copy(), w.ep_ret_done.copy() if mon else None,
+                                        w.ep_len_done.copy() if mon else None, self._t_start, mon)
+        return obs, rew, done, infos
 
     def step(self, actions):
         self.step_async(actions)
@@ -339,6 +437,38 @@ class DeviceVecNormalize:
 
     def seed(self, seed=None):
         return self.venv.seed(seed)
+
+
+class _HostOut:
+    """The wrapper's host-mapped output block (he_host_alloc; _layout.IoLayout vn_*): what the host
+    reads of a VecNormalize step -- normalized [obs | reward] (as _io_out), the normalized terminal
+    obs and the finished episodes' Monitor return and length.  The statistics, the returns and the
+    running Monitor sums stay in device memory (the kernel reads them back every step)."""
+
+    def __init__(self, w):
+        lib, n, L = w.lib, w.num_envs, w._layout
+        c = ctypes
+        self.lib = lib
+        hp, dp = c.c_void_p(), c.c_void_p()
+        _lib.check(lib, None, lib.he_host_alloc(L.vn_host_total, c.byref(hp), c.byref(dp)), "he_host_alloc")
+        self.host = hp.value
+        base = np.frombuffer((c.c_uint8 * L.vn_host_total).from_address(hp.value), np.uint8)
+        d = dp.value
+        D = _lib.HE_OBS_DIM
+        self.io = base[:L.terminated]
+        self.tobs = base[L.vn_terminal_obs:L.vn_ep_ret_done].view(np.float32)[:n * D].reshape(n, D)
+        self.ep_ret_done = base[L.vn_ep_ret_done:L.vn_ep_len_done].view(np.float64)[:n]
+        self.ep_len_done = base[L.vn_ep_len_done:L.vn_host_total].view(np.int32)[:n]
+        mon = (w._ep_ret.data_ptr(), w._ep_len.data_ptr(), d + L.vn_ep_ret_done, d + L.vn_ep_len_done) \
+            if w._monitor else (None,) * 4
+        self.out = _lib.HeVecnormOut(w._stats.data_ptr(), w._returns.data_ptr(), d, d + L.reward,
+                                     d + L.vn_terminal_obs, *mon)
+        self.out_ref = c.byref(self.out)
+
+    def free(self):
+        if self.host:
+            self.lib.he_host_free(self.host)
+            self.host = None
 
 
 class _NormInfoView(InfoView):

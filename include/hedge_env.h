@@ -321,7 +321,8 @@ he_status he_stream_wait(void* stream);
  * signalled step by reading the word through its HOST address: a short spin, then (a step queued behind
  * long work) hipStreamSynchronize(stream) and a final check (HE_ESTATE if the flag still differs).
  * It replaces he_stream_wait when that step is the last work on the stream the caller waits for;
- * he_step with VecNormalize attached refuses the signal (HE_EINVAL).  A handle's first
+ * he_step with VecNormalize attached refuses the signal (HE_EINVAL), except the whole step of
+ * he_vecnorm_attach_step, which raises it after its own outputs.  A handle's first
  * he_step_signal allocates the device word that counts the step's workgroups (a device
  * synchronize, once); later calls only arm.  The kernel's end is still
  * reported to the runtime as usual, so later stream-ordered work and events are unaffected. */
@@ -471,6 +472,28 @@ typedef struct he_vecnorm_out {
     int32_t* ep_length_done;
 } he_vecnorm_out;
 he_status he_vecnorm_attach_eval(he_env* env, const he_vecnorm_params* p, const he_vecnorm_out* out);
+
+/* The whole step inside he_step's launch for up to HE_VN_STEP_MAX_ENVS envs -- the wrapped
+ * stack the reference's agents drive, VecNormalize(Monitor(HedgingEnv)) over N_ENVS = 2
+ * (train_ppo_v2.py:45,119,204,305; frozen at :450-453).  That many envs are one step
+ * workgroup, so no part of the step crosses workgroups: he_vecnorm_attach_step arms the NEXT
+ * he_step on `env` (one-shot, consumed by that call whatever its status; p = NULL disarms) to
+ * do all of he_vecnorm_step's work itself -- p->training 0 or 1, either p->moments, the
+ * Monitor sums from the step's own f64 rewards -- with or without info fields requested, and
+ * with the bits of the same he_step followed by he_vecnorm_step (moments = HE_VN_MOMENTS_F64:
+ * of he_vecnorm_attach + that he_step + he_vecnorm_apply, whose sums take one order when the
+ * step requests info fields and another when it does not).  out's buffers
+ * may be device memory or he_host_alloc'd memory (obs_out, reward_out, terminal_obs_out,
+ * ep_return_done, ep_length_done are only written; stats, returns, ep_return, ep_length are
+ * read too: keep them on the device).  An he_step_signal armed for the same step is honoured:
+ * its word is stored after the VecNormalize outputs, so a host caller's step is one launch
+ * and one he_signal_wait.  he_step must get the obs, reward, terminated and terminal_obs
+ * buffers (HE_EINVAL otherwise).  `scratch` (he_vecnorm_scratch_bytes) is not used by one
+ * workgroup and may be NULL.  HE_EINVAL with a message: more than HE_VN_STEP_MAX_ENVS envs, a
+ * liability book or autoreset = 0 (no kernel: use he_vecnorm_attach / he_vecnorm_step), bad params, or out
+ * members missing by he_vecnorm_attach_eval's rules. */
+#define HE_VN_STEP_MAX_ENVS 256
+he_status he_vecnorm_attach_step(he_env* env, const he_vecnorm_params* p, const he_vecnorm_out* out, void* scratch);
 
 /* VecNormalize.reset: returns = 0; obs_rms.update(obs) (training && norm_obs);
  * obs_out normalized (norm_obs, else a copy). */
