@@ -16,6 +16,8 @@ reference's Python interface on top:
 * `DeviceAdam` -- the gradient-norm clip and Adam's step over all parameters in two launches
   (train.py); `RecurrentPolicy.load_device_state_dict` re-packs the policy from device tensors in one
   launch (agent.py): a training iteration without a host round trip
+* `ppo_loss_kernel` -- RecurrentPPO.train's loss, its statistics and its gradients with respect to
+  values, log_prob and entropy as kernels with an arithmetic contract (train.py, ha_ppo_loss)
 """
 __version__ = "0.1.0"
 
@@ -36,7 +38,8 @@ def __getattr__(name):
     if name == "RolloutCollector":
         from .collect import RolloutCollector
         return RolloutCollector
-    if name in ("lstm_sequence", "lstm_sequence_pair", "RecurrentPPOModule", "ppo_update", "DeviceAdam"):
+    if name in ("lstm_sequence", "lstm_sequence_pair", "RecurrentPPOModule", "ppo_update", "DeviceAdam",
+                "ppo_loss_kernel"):
         from . import train
         return getattr(train, name)
     raise AttributeError(name)

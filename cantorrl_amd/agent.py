@@ -120,6 +120,9 @@ SIG = {
     "ha_adam_workspace_bytes": (ctypes.c_size_t, [_i64, _vp]),
     "ha_adam_step": (_i32, [_i64, _vp, _vp, _vp, _vp]),
     "ha_host_adam_step": (_i32, [_i64, _vp, _vp]),
+    "ha_ppo_loss_workspace_bytes": (ctypes.c_size_t, [_i64]),
+    "ha_ppo_loss": (_i32, [_i64, _vp, _vp, _vp, _vp]),
+    "ha_host_ppo_loss": (_i32, [_i64, _vp, _vp]),
 }
 EXPORTS = list(SIG)
 

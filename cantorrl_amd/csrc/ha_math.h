@@ -1,6 +1,6 @@
 // ha_math.h -- the scalar arithmetic of the RecurrentPPO actor (include/hedge_actor.h,
-// "Arithmetic contract"), its rollout policy (sampling, log-probability) and GAE, shared by the
-// HIP kernels (__device__) and ha_host_step / ha_host_policy_step / ha_host_gae (__host__):
+// "Arithmetic contract"), its rollout policy (sampling, log-probability), GAE, the optimizer step and
+// the PPO loss, shared by the HIP kernels (__device__) and the ha_host_* entry points (__host__):
 // one implementation, so the two agree bit for bit.  The library is compiled with
 // -ffp-contract=off; f64 + - * / are IEEE on both sides and he::exp_k is host / device identical.
 #pragma once
@@ -195,6 +195,80 @@ HE_HD void adam_element(float g, float c, const AdamConsts& k, float* p, float* 
     *m = mn;
     *v = vn;
     *p = *p - u;
+}
+
+// ---------------------------------------------------------------- the PPO loss (ha_ppo_loss)
+// the constants of contract L4-L6, formed once on the host
+struct LossConsts {
+    double c, lo, hi, cv, ent_coef, vf_coef, vf2, n;   // lo = 1 - c, hi = 1 + c, vf2 = 2 vf_coef, n = f64(N)
+    int normalize, clip_vf;
+};
+
+// Contract L3: the spread of the advantages from the sum of squared deviations
+HE_HD double loss_std(double ssq, double n) {
+    const double var = ssq / (n - 1.0);
+    return sqrt(var);
+}
+
+// the five terms of L5's sums
+struct LossTerms {
+    double pol, val, ent, kl, clipped;
+};
+
+// Contract L3 (the row's A'), L4 and L6 for one row; den = std + 1e-8.  One f64 rounding per line.
+HE_HD LossTerms loss_row(float v, float lp, float ent, float old_lp, float adv, float ret, float old_v, double mean,
+                         double den, const LossConsts& k, float* d_v, float* d_lp) {
+    double a = (double)adv;
+    if (k.normalize) {
+        const double dev = a - mean;
+        a = dev / den;
+    }
+    const double d = (double)lp - (double)old_lp;
+    const double r = he::exp_k(d);
+    const double rc = r < k.lo ? k.lo : (r > k.hi ? k.hi : r);
+    const double s1 = a * r;
+    const double s2 = a * rc;
+    const bool active = (a >= 0.0) ? (r < k.hi) : (r > k.lo);
+    double vp = (double)v;
+    bool pass = true;
+    if (k.clip_vf) {
+        const double dv = (double)v - (double)old_v;
+        const double cl = dv < -k.cv ? -k.cv : (dv > k.cv ? k.cv : dv);
+        vp = (double)old_v + cl;
+        pass = fabs(dv) <= k.cv;
+    }
+    const double e = (double)ret - vp;
+    const double r1 = r - 1.0;
+    LossTerms t;
+    t.pol = s2 < s1 ? s2 : s1;
+    t.val = e * e;
+    t.ent = (double)ent;
+    t.kl = r1 - d;
+    t.clipped = fabs(r1) > k.c ? 1.0 : 0.0;
+    const double gl = -s1;
+    const double ge = k.vf2 * e;
+    const double gv = -ge;
+    *d_lp = active ? (float)(gl / k.n) : 0.0f;
+    *d_v = pass ? (float)(gv / k.n) : 0.0f;
+    return t;
+}
+
+// Contract L5 from the five totals, mean and std: the eight statistics, each rounded once
+HE_HD void loss_stats(const double* tot, double mean, double sd, const LossConsts& k, float* stats) {
+    const double policy = -tot[0] / k.n;
+    const double value = tot[1] / k.n;
+    const double entropy = -tot[2] / k.n;
+    const double pe = k.ent_coef * entropy;
+    const double l1 = policy + pe;
+    const double vv = k.vf_coef * value;
+    stats[0] = (float)(l1 + vv);
+    stats[1] = (float)policy;
+    stats[2] = (float)value;
+    stats[3] = (float)entropy;
+    stats[4] = (float)(tot[3] / k.n);
+    stats[5] = (float)(tot[4] / k.n);
+    stats[6] = (float)mean;
+    stats[7] = (float)sd;
 }
 
 }  // namespace ha

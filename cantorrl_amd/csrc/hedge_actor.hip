@@ -26,8 +26,8 @@
 // stage the same obs; registers and LDS stay at actor_kernel's figures.  gae_kernel (ha_gae) is
 // one thread per env over [K][n] arrays.  lstm_seq_fwd_kernel / lstm_seq_bwd_kernel (the PPO update's
 // LSTM over a stored sequence, forward and backward) and lstm_wgrad_kernel / lstm_wgrad_reduce_kernel
-// (its weight gradients), policy_pack_kernel (ha_policy_refresh) and opt_norm_kernel / opt_adam_kernel
-// (ha_adam_step) are described where they stand.
+// (its weight gradients), policy_pack_kernel (ha_policy_refresh), opt_norm_kernel / opt_adam_kernel
+// (ha_adam_step) and the four loss_*_kernel (ha_ppo_loss) are described where they stand.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -1345,6 +1345,235 @@ ha_status check_adam(int64_t n, const ha_adam_tensor* ts, const ha_adam_hyper* h
     return HE_OK;
 }
 
+// ---------------------------------------------------------------- the PPO loss (contract L1-L6)
+// One workgroup of 256 per block of HA_LOSS_BLOCK rows; lane i owns rows i, i + 256, ... of its block
+// (L1), so a wave's load is 256 consecutive bytes of each array.  The blocks' sums go to the workspace
+// as f64, [sum A | sum (A - mean)^2 | pol | val | ent | kl | clipped][block]; the launch after reads them:
+//   loss_mean_kernel    s_b of L2.
+//   loss_spread_kernel  every workgroup adds the s_b of L2 in block order (loss_totals: the same adds
+//                       everywhere, the same bits) and forms its s_b of L3.
+//   loss_rows_kernel    both lists' totals (lanes 0 and 1, one chain each), the row's loads in flight
+//                       meanwhile; loss_row per row, the gradients stored, the five s_b of L5 through one
+//                       tree.
+//   loss_stats_kernel   one workgroup: lane l < 7 adds list l in block order, lane 0 forms the statistics.
+// The serial totals bound a large call, as O2 bounds ha_adam_step: HA_LOSS_MAX_BLOCKS is the cap.
+constexpr int kLossLanes = 256, kLossPerLane = HA_LOSS_BLOCK / kLossLanes, kLossLists = 7, kLossStage = 512;
+static_assert(HA_LOSS_BLOCK % kLossLanes == 0 && kLossPerLane >= 1, "whole rows a lane");
+static_assert((int64_t)HA_LOSS_BLOCK * HA_LOSS_MAX_BLOCKS >= (int64_t)256 * 16384, "a 256 x 16,384 buffer is one call");
+
+struct LossParams {
+    ha_ppo_loss_io io;
+    LossConsts k;
+    int64_t n;
+    int32_t nb;
+    double* ws;   // [kLossLists][nb]
+};
+
+// the tree of O1 over NQ lists of 256 lane sums at once; q[j][0] is list j's s_b (read by lane 0)
+template <int NQ>
+__device__ __forceinline__ void loss_tree(double (*q)[kLossLanes], int tid) {
+    for (int off = kLossLanes / 2; off >= 1; off >>= 1) {
+        __syncthreads();
+        if (tid < off) {
+#pragma unroll
+            for (int j = 0; j < NQ; ++j) q[j][tid] = q[j][tid] + q[j][tid + off];
+        }
+    }
+}
+
+// L1's totals of NL lists of nb block sums that lie nb apart from `lists`: the blocks' sums are staged in
+// LDS kLossStage blocks at a time by all lanes (coalesced loads, no chain of load latencies), and lane
+// l < NL adds list l from 0.0 in block order.  Every workgroup makes the same adds in the same order:
+// the same bits.  On return (after a barrier) tot[l] holds list l's total.
+template <int NL>
+__device__ __forceinline__ void loss_totals(const double* __restrict__ lists, int nb, int tid, double* stage,
+                                            double* tot) {
+    double t = 0.0;
+    for (int j0 = 0; j0 < nb; j0 += kLossStage) {
+        const int cnt = nb - j0 < kLossStage ? nb - j0 : kLossStage;
+        __syncthreads();   // the chunk before is consumed (and, the first time, LDS of the caller's is free)
+        for (int j = tid; j < cnt; j += kLossLanes) {
+#pragma unroll
+            for (int l = 0; l < NL; ++l) stage[j * NL + l] = lists[(int64_t)l * nb + j0 + j];
+        }
+        __syncthreads();
+        if (tid < NL) {
+#pragma unroll 8
+            for (int j = 0; j < cnt; ++j) t = t + stage[j * NL + tid];
+        }
+    }
+    if (tid < NL) tot[tid] = t;
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kLossLanes) void loss_mean_kernel(const LossParams p) {
+    __shared__ double q[1][kLossLanes];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* __restrict__ adv = p.io.advantages;
+    double s = 0.0;
+#pragma unroll
+    for (int m = 0; m < kLossPerLane; ++m) {
+        const int64_t i = (int64_t)b * HA_LOSS_BLOCK + m * kLossLanes + tid;
+        s = s + (i < p.n ? (double)adv[i] : 0.0);
+    }
+    q[0][tid] = s;
+    loss_tree<1>(q, tid);
+    if (tid == 0) p.ws[b] = q[0][0];
+}
+
+__global__ __launch_bounds__(kLossLanes) void loss_spread_kernel(const LossParams p) {
+    __shared__ double q[1][kLossLanes];
+    __shared__ double stage[kLossStage];
+    __shared__ double tot[1];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* __restrict__ adv = p.io.advantages;
+    float a[kLossPerLane];
+#pragma unroll
+    for (int m = 0; m < kLossPerLane; ++m) {
+        const int64_t i = (int64_t)b * HA_LOSS_BLOCK + m * kLossLanes + tid;
+        a[m] = i < p.n ? adv[i] : 0.0f;
+    }
+    loss_totals<1>(p.ws, p.nb, tid, stage, tot);
+    const double mean = tot[0] / p.k.n;
+    double s = 0.0;
+#pragma unroll
+    for (int m = 0; m < kLossPerLane; ++m) {
+        const int64_t i = (int64_t)b * HA_LOSS_BLOCK + m * kLossLanes + tid;
+        const double dev = (double)a[m] - mean;
+        s = s + (i < p.n ? dev * dev : 0.0);
+    }
+    q[0][tid] = s;
+    loss_tree<1>(q, tid);
+    if (tid == 0) p.ws[p.nb + b] = q[0][0];
+}
+
+__global__ __launch_bounds__(kLossLanes) void loss_rows_kernel(const LossParams p) {
+    __shared__ double q[5][kLossLanes];
+    __shared__ double stage[2 * kLossStage];
+    __shared__ double tot[2];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const ha_ppo_loss_io& io = p.io;
+    float v[kLossPerLane], lp[kLossPerLane], en[kLossPerLane], ol[kLossPerLane], ad[kLossPerLane], re[kLossPerLane],
+        ov[kLossPerLane];
+#pragma unroll
+    for (int m = 0; m < kLossPerLane; ++m) {
+        const int64_t i = (int64_t)b * HA_LOSS_BLOCK + m * kLossLanes + tid;
+        const bool in = i < p.n;
+        v[m] = in ? io.values[i] : 0.0f;
+        lp[m] = in ? io.log_prob[i] : 0.0f;
+        en[m] = in ? io.entropy[i] : 0.0f;
+        ol[m] = in ? io.old_log_prob[i] : 0.0f;
+        ad[m] = in ? io.advantages[i] : 0.0f;
+        re[m] = in ? io.returns[i] : 0.0f;
+        ov[m] = (in && p.k.clip_vf) ? io.old_values[i] : 0.0f;
+    }
+    double mean = 0.0, den = 1.0;
+    if (p.k.normalize) {
+        loss_totals<2>(p.ws, p.nb, tid, stage, tot);
+        mean = tot[0] / p.k.n;
+        den = loss_std(tot[1], p.k.n) + 1e-8;
+    }
+    const double ge = -p.k.ent_coef;
+    const float d_ent = (float)(ge / p.k.n);
+    double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int m = 0; m < kLossPerLane; ++m) {
+        const int64_t i = (int64_t)b * HA_LOSS_BLOCK + m * kLossLanes + tid;
+        const bool in = i < p.n;
+        float d_v, d_lp;
+        const LossTerms t = loss_row(v[m], lp[m], en[m], ol[m], ad[m], re[m], ov[m], mean, den, p.k, &d_v, &d_lp);
+        s[0] = s[0] + (in ? t.pol : 0.0);
+        s[1] = s[1] + (in ? t.val : 0.0);
+        s[2] = s[2] + (in ? t.ent : 0.0);
+        s[3] = s[3] + (in ? t.kl : 0.0);
+        s[4] = s[4] + (in ? t.clipped : 0.0);
+        if (in) {
+            io.d_values[i] = d_v;
+            io.d_log_prob[i] = d_lp;
+            io.d_entropy[i] = d_ent;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 5; ++j) q[j][tid] = s[j];
+    loss_tree<5>(q, tid);
+    if (tid < 5) p.ws[(int64_t)(2 + tid) * p.nb + b] = q[tid][0];
+}
+
+__global__ __launch_bounds__(kLossLanes) void loss_stats_kernel(const LossParams p) {
+    __shared__ double stage[kLossLists * kLossStage];
+    __shared__ double tot[kLossLists];
+    const int tid = threadIdx.x;
+    if (p.k.normalize)
+        loss_totals<kLossLists>(p.ws, p.nb, tid, stage, tot);
+    else
+        loss_totals<kLossLists - 2>(p.ws + 2 * (int64_t)p.nb, p.nb, tid, stage, tot + 2);
+    if (tid == 0) {
+        const double mean = p.k.normalize ? tot[0] / p.k.n : 0.0;
+        const double sd = p.k.normalize ? loss_std(tot[1], p.k.n) : 1.0;
+        loss_stats(tot + 2, mean, sd, p.k, p.io.stats);
+    }
+}
+
+// The checks of ha_ppo_loss / ha_host_ppo_loss; fills the constants (io, hy and k NULL: n_rows alone,
+// for the workspace's size).
+ha_status check_loss(int64_t n, const ha_ppo_loss_io* io, const ha_ppo_loss_hyper* hy, LossConsts* k) {
+    char m[200];
+    if (n < 1 || n > (int64_t)HA_LOSS_BLOCK * HA_LOSS_MAX_BLOCKS) {
+        snprintf(m, sizeof m, "n_rows = %lld: 1 to %lld rows a call (%d blocks of %d)", (long long)n,
+                 (long long)HA_LOSS_BLOCK * HA_LOSS_MAX_BLOCKS, HA_LOSS_MAX_BLOCKS, HA_LOSS_BLOCK);
+        return fail_to(nullptr, HE_ESHAPE, m);
+    }
+    if (!k) return HE_OK;
+    if (!io || !hy) return fail_to(nullptr, HE_EINVAL, "io or hyper is NULL");
+    if (n == 1 && hy->normalize_advantage)
+        return fail_to(nullptr, HE_ESHAPE, "n_rows = 1 with normalize_advantage: the unbiased std needs two rows");
+    const double inf = __builtin_inf();
+    if (!(hy->clip_range >= 0.0 && hy->clip_range < inf))
+        return fail_to(nullptr, HE_EINVAL, "clip_range must be finite and >= 0");
+    const bool clip_vf = hy->clip_range_vf > 0.0;
+    if (clip_vf && !io->old_values) return fail_to(nullptr, HE_EINVAL, "clip_range_vf > 0 needs old_values");
+    const void* ptrs[] = {io->values,  io->log_prob, io->entropy,    io->old_log_prob, io->advantages,
+                          io->returns, io->d_values, io->d_log_prob, io->d_entropy,    io->stats};
+    uintptr_t bits = clip_vf ? (uintptr_t)io->old_values : 0;
+    for (const void* q : ptrs) {
+        if (!q) return fail_to(nullptr, HE_EINVAL, "a pointer of io is NULL");
+        bits |= (uintptr_t)q;
+    }
+    if (bits & 3u) return fail_to(nullptr, HE_EINVAL, "the pointers of io must be 4-byte aligned");
+    k->c = hy->clip_range;
+    k->lo = 1.0 - k->c;
+    k->hi = 1.0 + k->c;
+    k->cv = clip_vf ? hy->clip_range_vf : 0.0;
+    k->ent_coef = hy->ent_coef;
+    k->vf_coef = hy->vf_coef;
+    k->vf2 = 2.0 * hy->vf_coef;
+    k->n = (double)n;
+    k->normalize = hy->normalize_advantage != 0;
+    k->clip_vf = clip_vf;
+    return HE_OK;
+}
+
+// L1 on the host over rows [0, n): term(row) in f64, a short last block padded with +0
+template <class F>
+double loss_sum_host(int64_t n, F term) {
+    double total = 0.0;
+    for (int64_t b0 = 0; b0 < n; b0 += HA_LOSS_BLOCK) {
+        double q[kLossLanes];
+        for (int i = 0; i < kLossLanes; ++i) {
+            double s = 0.0;
+            for (int m = 0; m < kLossPerLane; ++m) {
+                const int64_t r = b0 + m * kLossLanes + i;
+                s = s + (r < n ? term(r) : 0.0);
+            }
+            q[i] = s;
+        }
+        for (int off = kLossLanes / 2; off >= 1; off >>= 1)
+            for (int i = 0; i < off; ++i) q[i] = q[i] + q[i + off];
+        total = total + q[0];
+    }
+    return total;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1860,6 +2089,72 @@ ha_status ha_host_adam_step(int64_t n_tensors, const ha_adam_tensor* tensors, co
         const ha_adam_tensor& t = tensors[j];
         for (int64_t i = 0; i < t.numel; ++i) adam_element(t.grad[i], c, k, t.param + i, t.exp_avg + i, t.exp_avg_sq + i);
     }
+    return HE_OK;
+}
+
+size_t ha_ppo_loss_workspace_bytes(int64_t n_rows) {
+    if (check_loss(n_rows, nullptr, nullptr, nullptr) != HE_OK) return 0;
+    return (size_t)((n_rows - 1) / HA_LOSS_BLOCK + 1) * kLossLists * sizeof(double);
+}
+
+ha_status ha_ppo_loss(int64_t n_rows, const ha_ppo_loss_io* io, const ha_ppo_loss_hyper* hyper, void* workspace,
+                      void* stream) {
+    LossParams p;
+    ha_status st = check_loss(n_rows, io, hyper, &p.k);
+    if (st != HE_OK) return st;
+    if (!workspace || (((uintptr_t)workspace) & 7u))
+        return fail_to(nullptr, HE_EINVAL, "workspace must be non-NULL and 8-byte aligned");
+    p.io = *io;
+    p.n = n_rows;
+    p.nb = (int32_t)((n_rows - 1) / HA_LOSS_BLOCK + 1);
+    p.ws = (double*)workspace;
+    const dim3 grid((unsigned)p.nb), block(kLossLanes);
+    if (p.k.normalize) {
+        st = launch(nullptr, loss_mean_kernel, grid, block, stream, "loss_mean_kernel", p);
+        if (st != HE_OK) return st;
+        st = launch(nullptr, loss_spread_kernel, grid, block, stream, "loss_spread_kernel", p);
+        if (st != HE_OK) return st;
+    }
+    st = launch(nullptr, loss_rows_kernel, grid, block, stream, "loss_rows_kernel", p);
+    if (st != HE_OK) return st;
+    return launch(nullptr, loss_stats_kernel, dim3(1), block, stream, "loss_stats_kernel", p);
+}
+
+ha_status ha_host_ppo_loss(int64_t n_rows, const ha_ppo_loss_io* io, const ha_ppo_loss_hyper* hyper) {
+    LossConsts k;
+    const ha_status st = check_loss(n_rows, io, hyper, &k);
+    if (st != HE_OK) return st;
+    std::vector<LossTerms> t;
+    try {
+        t.resize((size_t)n_rows);
+    } catch (const std::bad_alloc&) {
+        return fail_to(nullptr, HE_ENOMEM, "out of host memory");
+    }
+    double mean = 0.0, sd = 1.0, den = 1.0;
+    if (k.normalize) {   // L2, L3
+        const float* adv = io->advantages;
+        mean = loss_sum_host(n_rows, [&](int64_t r) { return (double)adv[r]; }) / k.n;
+        const double ssq = loss_sum_host(n_rows, [&](int64_t r) {
+            const double dev = (double)adv[r] - mean;
+            return dev * dev;
+        });
+        sd = loss_std(ssq, k.n);
+        den = sd + 1e-8;
+    }
+    const double ge = -k.ent_coef;
+    const float d_ent = (float)(ge / k.n);
+    for (int64_t r = 0; r < n_rows; ++r) {   // L4, L6
+        t[(size_t)r] = loss_row(io->values[r], io->log_prob[r], io->entropy[r], io->old_log_prob[r], io->advantages[r],
+                                io->returns[r], k.clip_vf ? io->old_values[r] : 0.0f, mean, den, k, io->d_values + r,
+                                io->d_log_prob + r);
+        io->d_entropy[r] = d_ent;
+    }
+    const double tot[5] = {loss_sum_host(n_rows, [&](int64_t r) { return t[(size_t)r].pol; }),
+                           loss_sum_host(n_rows, [&](int64_t r) { return t[(size_t)r].val; }),
+                           loss_sum_host(n_rows, [&](int64_t r) { return t[(size_t)r].ent; }),
+                           loss_sum_host(n_rows, [&](int64_t r) { return t[(size_t)r].kl; }),
+                           loss_sum_host(n_rows, [&](int64_t r) { return t[(size_t)r].clipped; })};
+    loss_stats(tot, k.normalize ? mean : 0.0, sd, k, io->stats);   // L5
     return HE_OK;
 }
 

@@ -16,8 +16,11 @@ With opt = DeviceAdam(module.parameters(), lr=1e-4, eps=1e-5) the clip and the o
 libhedgeactor's ha_adam_step (two launches, contract O1-O5), and policy.load_device_state_dict(
 module.state_dict()) re-packs the policy on the device: an iteration without a host round trip.
 
-Only the LSTM is a kernel: nn.LSTM has no per-step reset, so sb3_contrib's _process_sequence runs one
-LSTM call per time step, forward and again in autograd's backward.  Here a workgroup walks all L
+With ppo_update(loss="kernel") the loss, its statistics and its gradients with respect to values,
+log_prob and entropy are libhedgeactor's ha_ppo_loss (ppo_loss_kernel, contract L1-L6).
+
+By default only the LSTM is a kernel: nn.LSTM has no per-step reset, so sb3_contrib's
+_process_sequence runs one LSTM call per time step, forward and again in autograd's backward.  Here a workgroup walks all L
 steps of its 32 envs inside one launch, actor and critic side by side.  The MLPs, the heads, the
 Gaussian log-probability, the loss and the optimizer are batched over L B rows and stay with torch.
 There is no torch fallback for the LSTM: a missing library is an error.  The LSTM's weight gradients are
@@ -353,14 +356,19 @@ class RecurrentPPOModule(torch.nn.Module):
 
 # --------------------------------------------------------------------------- the update
 def ppo_loss(values, log_prob, entropy, old_log_prob, advantages, returns, clip_range, ent_coef, vf_coef,
-             normalize_advantage=True):
-    """sb3_contrib 2.6.0 RecurrentPPO.train's loss for one minibatch without padding (mask all ones,
-    clip_range_vf None) -> (loss, stats)."""
+             normalize_advantage=True, clip_range_vf=None, old_values=None):
+    """sb3_contrib 2.6.0 RecurrentPPO.train's loss for one minibatch without padding (mask all ones)
+    -> (loss, stats).  clip_range_vf (None: no value clip) clips the value's move away from old_values,
+    the rollout's values of the same rows, as SB3 does."""
     adv = advantages
     if normalize_advantage:
         adv = (adv - adv.mean()) / (adv.std() + 1e-8)
     ratio = torch.exp(log_prob - old_log_prob)
     policy_loss = -torch.min(adv * ratio, adv * torch.clamp(ratio, 1 - clip_range, 1 + clip_range)).mean()
+    if clip_range_vf is not None:
+        if old_values is None:
+            raise ValueError("clip_range_vf needs old_values")
+        values = old_values + torch.clamp(values - old_values, -clip_range_vf, clip_range_vf)
     value_loss = ((returns - values) ** 2).mean()
     entropy_loss = -entropy.mean()
     loss = policy_loss + ent_coef * entropy_loss + vf_coef * value_loss
@@ -370,6 +378,65 @@ def ppo_loss(values, log_prob, entropy, old_log_prob, advantages, returns, clip_
                      entropy_loss=entropy_loss.detach(), approx_kl=((torch.exp(log_ratio) - 1) - log_ratio).mean(),
                      clip_fraction=(torch.abs(ratio - 1) > clip_range).float().mean())
     return loss, stats
+
+
+class HaPpoLossHyper(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in ("clip_range", "clip_range_vf", "ent_coef", "vf_coef")] + \
+               [("normalize_advantage", ctypes.c_int32)]
+
+
+class HaPpoLossIo(ctypes.Structure):
+    _fields_ = [(k, _VP) for k in ("values", "log_prob", "entropy", "old_log_prob", "advantages", "returns",
+                                   "old_values", "d_values", "d_log_prob", "d_entropy", "stats")]
+
+
+LOSS_BLOCK, LOSS_MAX_BLOCKS = 1024, 4096   # HA_LOSS_* of include/hedge_actor.h
+LOSS_STATS = ("loss", "policy_gradient_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction",
+              "adv_mean", "adv_std")       # the order of ha_ppo_loss_io.stats
+LOSSES = ("torch", "kernel")
+
+
+def ppo_loss_kernel(values, log_prob, entropy, old_log_prob, advantages, returns, clip_range, ent_coef, vf_coef,
+                    normalize_advantage=True, clip_range_vf=None, old_values=None):
+    """ppo_loss and its backward as libhedgeactor's ha_ppo_loss (contract L1-L6 of include/hedge_actor.h:
+    four launches, two without normalisation; CPU tensors run ha_host_ppo_loss, the same bits) ->
+    (stats, (d_values, d_log_prob, d_entropy)): ppo_loss's statistics plus adv_mean and adv_std as 0-d
+    tensors, and the loss's gradients with respect to the first three arguments in their shape.  The
+    inputs are float32 tensors of one shape on one device; they are detached.  Nothing synchronises with
+    the host.  A refusal of the library is a ValueError with its message."""
+    lib = load()
+    shape, dev = values.shape, values.device
+    names = ("values", "log_prob", "entropy", "old_log_prob", "advantages", "returns", "old_values")
+    given = (values, log_prob, entropy, old_log_prob, advantages, returns, old_values)
+    if clip_range_vf is None:
+        given, cv = given[:6], 0.0
+    else:
+        cv = float(clip_range_vf)
+        if not cv > 0.0:
+            raise ValueError(f"clip_range_vf = {clip_range_vf} must be > 0, or None for no value clip")
+        if old_values is None:
+            raise ValueError("clip_range_vf needs old_values")
+    io, keep = HaPpoLossIo(), []
+    for name, t in zip(names, given):
+        if t.dtype != torch.float32 or t.shape != shape or t.device != dev:
+            raise ValueError(f"{name} must be a float32 tensor of shape {tuple(shape)} on {dev}, not "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+        t = t.detach().contiguous()
+        keep.append(t)
+        setattr(io, name, t.data_ptr())
+    grads = tuple(torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(3))
+    out = torch.empty(len(LOSS_STATS), dtype=torch.float32, device=dev)
+    io.d_values, io.d_log_prob, io.d_entropy, io.stats = (*(g.data_ptr() for g in grads), out.data_ptr())
+    hy = HaPpoLossHyper(float(clip_range), cv, float(ent_coef), float(vf_coef), int(bool(normalize_advantage)))
+    n = values.numel()
+    if dev.type == "cpu":
+        st = lib.ha_host_ppo_loss(n, ctypes.byref(io), ctypes.byref(hy))
+    else:
+        with torch.cuda.device(dev):
+            ws = torch.empty(lib.ha_ppo_loss_workspace_bytes(n) or 8, dtype=torch.uint8, device=dev)
+            st = lib.ha_ppo_loss(n, ctypes.byref(io), ctypes.byref(hy), ws.data_ptr(), _stream(dev))
+    _check(lib, st, "ha_ppo_loss")
+    return dict(zip(LOSS_STATS, out.unbind(0))), grads
 
 
 class HaAdamTensor(ctypes.Structure):
@@ -503,7 +570,8 @@ def minibatch(buffer, idx, k0, k1):
 
 
 def ppo_update(module, optimizer, buffer, *, n_epochs=10, envs_per_batch=None, window=None, clip_range=0.3,
-               ent_coef=1e-5, vf_coef=0.5, max_grad_norm=0.5, normalize_advantage=True, generator=None):
+               ent_coef=1e-5, vf_coef=0.5, max_grad_norm=0.5, normalize_advantage=True, generator=None,
+               loss="torch", clip_range_vf=None):
     """RecurrentPPO.train over a collect.RolloutBuffer: n_epochs passes, each over a fresh permutation
     of the envs (from `generator`, a torch.Generator on the buffer's device) cut into groups of
     envs_per_batch (default: all), each group x each time window one optimizer step.  window=None: the
@@ -511,8 +579,13 @@ def ppo_update(module, optimizer, buffer, *, n_epochs=10, envs_per_batch=None, w
     collect(states=True) stores.  Defaults: the reference's default_hpo_params (train_ppo_v2.py:601-605:
     clip_range 0.3, ent_coef 1e-5, vf_coef 0.5, max_grad_norm 0.5, n_epochs 10).  An optimizer with a
     clip_and_step method (DeviceAdam) clips and steps through it, any other through clip_grad_norm_ and
-    step().  Nothing synchronises
+    step().  loss: "torch" is ppo_loss under autograd; "kernel" is ppo_loss_kernel (ha_ppo_loss, contract
+    L1-L6) on the heads' detached outputs, its three gradients handed to autograd where the heads stand.
+    clip_range_vf (None: no value clip) is SB3's, against buffer.values.  target_kl is not built.
+    Nothing synchronises
     with the host; returns the last minibatch's statistics and the mean loss as device scalars."""
+    if loss not in LOSSES:
+        raise ValueError(f"loss must be one of {LOSSES}, not {loss!r}")
     K, n = buffer.k_steps, buffer.n_envs
     W = K if window is None else int(window)
     if W < 1 or K % W:
@@ -533,10 +606,16 @@ def ppo_update(module, optimizer, buffer, *, n_epochs=10, envs_per_batch=None, w
                 mb = minibatch(buffer, idx, k0, k0 + W)
                 values, log_prob, entropy = module.evaluate_actions(mb["observations"], mb["actions"],
                                                                     mb["episode_starts"], mb["states0"])
-                loss, stats = ppo_loss(values, log_prob, entropy, mb["log_probs"], mb["advantages"], mb["returns"],
-                                       clip_range, ent_coef, vf_coef, normalize_advantage)
+                old_values = None if clip_range_vf is None else buffer.values[k0:k0 + W].index_select(1, idx)
+                args = (values, log_prob, entropy, mb["log_probs"], mb["advantages"], mb["returns"], clip_range,
+                        ent_coef, vf_coef, normalize_advantage, clip_range_vf, old_values)
                 optimizer.zero_grad(set_to_none=True)
-                loss.backward()
+                if loss == "kernel":
+                    stats, grads = ppo_loss_kernel(*args)
+                    torch.autograd.backward([values, log_prob, entropy], list(grads))
+                else:
+                    total_loss, stats = ppo_loss(*args)
+                    total_loss.backward()
                 if hasattr(optimizer, "clip_and_step"):   # DeviceAdam: the clip and the step in two launches
                     stats["grad_norm"] = optimizer.clip_and_step(max_grad_norm)
                 else:

@@ -5,8 +5,8 @@
  * per-episode sums of a closed-loop evaluation around he_step, and the training side: actor,
  * critic, action sampling and log-probability of a rollout step in one launch, GAE, and for the
  * PPO update both LSTMs over a stored sequence with per-step resets, forward and backward, their
- * weight gradients, the gradient-norm clip with Adam's step, and the re-packing of a policy's handle
- * from the updated device tensors.
+ * weight gradients, the PPO loss with its gradients, the gradient-norm clip with Adam's step, and the
+ * re-packing of a policy's handle from the updated device tensors.
  *
  * Conventions (as hedge_env.h): plain C types, every entry point returns an ha_status (the
  * he_status values), the last failure's message is ha_last_error(handle), no C++ exception
@@ -126,6 +126,35 @@
  *       f32 / and sqrtf are correctly rounded on the device (-fhip-fp32-correctly-rounded-divide-sqrt).
  *   Nothing in O1-O5 depends on the grid; a tensor cut at a multiple of 256 elements into two tensors
  *   standing where it stood gives the same blocks, hence the same bits.
+ *
+ * The PPO loss (ha_ppo_loss: sb3_contrib 2.6.0 RecurrentPPO.train's loss for one minibatch of N rows
+ * without padding, its six statistics and its gradients with respect to values, log_prob and entropy in
+ * closed form; restated).  Everything in f64 from the f32 inputs, every operation rounded once, in the
+ * order written, no contraction; c = clip_range, cv = clip_range_vf.  Per row i: v = values, lp =
+ * log_prob, ent = entropy, old_lp, A = advantages, ret = returns, old_v = old_values.
+ *   L1. a sum: the rows are cut into blocks of HA_LOSS_BLOCK consecutive rows, a short last block
+ *       padded with terms +0.  Lane i of 256 adds the terms of its rows i, i + 256, ... of the block
+ *       from 0.0 in ascending order: q_i.  Then the tree of O1: q_i += q_(i + 128) for i < 128, ...
+ *       q_0 += q_1; s_b = q_0.  The total is the f64 sum from 0.0 of s_b over the blocks in order.
+ *       Every sum below is this sum.
+ *   L2. mean = sum f64(A_i) / N.
+ *   L3. with normalize_advantage: std = sqrt(sum (f64(A_i) - mean)^2 / (N - 1)) (unbiased) and
+ *       A'_i = (f64(A_i) - mean) / (std + 1e-8).  Without: A'_i = f64(A_i), and the statistics report
+ *       mean 0, std 1.  f64 / and sqrt are correctly rounded, as in O3.
+ *   L4. per row: d = f64(lp) - f64(old_lp) (exact), r = he::exp_k(d), lo = 1 - c, hi = 1 + c,
+ *       rc = r < lo ? lo : (r > hi ? hi : r); s1 = A' r, s2 = A' rc, pol = s2 < s1 ? s2 : s1;
+ *       active = (A' >= 0) ? (r < hi) : (r > lo).
+ *       vp = f64(v) and pass = true without a value clip (cv <= 0); with one, dv = f64(v) - f64(old_v),
+ *       vp = f64(old_v) + (dv < -cv ? -cv : (dv > cv ? cv : dv)), pass = |dv| <= cv (torch.clamp passes
+ *       gradient on the closed interval).
+ *       e = f64(ret) - vp, val = e e, kl = (r - 1) - d, clipped = |r - 1| > c (1.0 or 0.0).
+ *   L5. policy = -(sum pol) / N, value = sum val / N, entropy_loss = -(sum f64(ent)) / N,
+ *       loss = (policy + ent_coef entropy_loss) + vf_coef value, approx_kl = sum kl / N,
+ *       clip_fraction = sum clipped / N.  stats = { loss, policy, value, entropy_loss, approx_kl,
+ *       clip_fraction, mean, std }, each rounded once to f32.
+ *   L6. d_log_prob_i = active ? -(A' r) / N : +0; d_values_i = pass ? -((2 vf_coef) e) / N : +0;
+ *       d_entropy_i = -ent_coef / N; each rounded once to f32.
+ *   Nothing in L1-L6 depends on the grid.
  */
 #ifndef HEDGE_ACTOR_H
 #define HEDGE_ACTOR_H
@@ -448,6 +477,55 @@ ha_status ha_adam_step(int64_t n_tensors, const ha_adam_tensor* tensors, const h
 
 /* The same arithmetic on the host, HOST pointers throughout, no workspace. */
 ha_status ha_host_adam_step(int64_t n_tensors, const ha_adam_tensor* tensors, const ha_adam_hyper* hyper);
+
+/* ---- the PPO loss: statistics and the gradients of values, log_prob, entropy (L1-L6) ---- */
+#define HA_LOSS_BLOCK 1024       /* rows of one block of L1: four rows a lane of 256 */
+#define HA_LOSS_MAX_BLOCKS 4096  /* blocks of one call: 2^22 rows, a 256 x 16,384 buffer as one minibatch */
+
+typedef struct ha_ppo_loss_hyper {
+    double clip_range;
+    double clip_range_vf; /* <= 0 or NaN: no value clip */
+    double ent_coef;
+    double vf_coef;
+    int32_t normalize_advantage;
+} ha_ppo_loss_hyper;
+
+/* DEVICE pointers (HOST pointers for ha_host_ppo_loss), n_rows f32 each, 4-byte aligned. */
+typedef struct ha_ppo_loss_io {
+    const float* values;
+    const float* log_prob;
+    const float* entropy;
+    const float* old_log_prob;
+    const float* advantages;
+    const float* returns;
+    const float* old_values; /* required iff clip_range_vf > 0, else ignored (may be NULL) */
+    float* d_values;
+    float* d_log_prob;
+    float* d_entropy;
+    float* stats;            /* [8]: loss, policy_gradient_loss, value_loss, entropy_loss, approx_kl,
+                                clip_fraction, adv_mean, adv_std (0, 1 without normalisation) */
+} ha_ppo_loss_io;
+
+/* Bytes of ha_ppo_loss's workspace: seven f64 per block (the s_b of L2's, L3's and L5's five sums).
+ * 0 for an n_rows the call refuses.  The workspace carries nothing from call to call. */
+size_t ha_ppo_loss_workspace_bytes(int64_t n_rows);
+
+/* L1-L6 over n_rows rows, one workgroup of 256 per block of HA_LOSS_BLOCK rows.  With normalisation four
+ * launches: loss_mean_kernel writes each block's sum of A, loss_spread_kernel (every workgroup adds
+ * those in block order: the same bits everywhere) each block's sum of squared deviations,
+ * loss_rows_kernel the three gradients and each block's five sums, loss_stats_kernel (one workgroup)
+ * the eight statistics.  Without normalisation the last two alone.  No atomics, no waiting between
+ * workgroups: kernel boundaries are the only grid-wide ordering.  Stream-ordered: no host
+ * synchronisation, no copy call, no allocation; the workspace (8-byte aligned) is the caller's.  Before
+ * any launch: n_rows outside [1, HA_LOSS_BLOCK HA_LOSS_MAX_BLOCKS], or n_rows = 1 with
+ * normalize_advantage (an unbiased std of one row), is HE_ESHAPE; a NULL or misaligned pointer, a
+ * missing old_values when clip_range_vf > 0, a clip_range that is negative or not finite HE_EINVAL.
+ * The message is ha_policy_last_error(NULL). */
+ha_status ha_ppo_loss(int64_t n_rows, const ha_ppo_loss_io* io, const ha_ppo_loss_hyper* hyper, void* workspace,
+                      void* stream);
+
+/* The same arithmetic on the host (L1-L6 taken literally), HOST pointers, no workspace. */
+ha_status ha_host_ppo_loss(int64_t n_rows, const ha_ppo_loss_io* io, const ha_ppo_loss_hyper* hyper);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,7 @@ autograd, f32.  And one ppo_update epoch over a buffer of the first shape.  HIP 
 call, warm-up first, the median.
 
     python tools/train_time.py [--reps R] [--out FILE.jsonl] [--shapes L,B ...] [--weight-grads torch|kernel|both]
-                               [--optimizer]
+                               [--optimizer] [--loss]
 
 --weight-grads torch (the default) times lstm_sequence_pair as it is called by default, its weight
 gradients from train.weight_grads.  kernel times forward plus backward with weight_grads="kernel", and
@@ -26,6 +26,12 @@ torch.optim.Adam.step() (default and fused=True) against train.DeviceAdam.clip_a
 wall time to completion), RecurrentPolicy.load_state_dict against load_device_state_dict (wall time with
 the Python call included: until the call returns, and until the device is done), and one ppo_update
 epoch per --shapes entry with each optimizer.
+
+--loss times, instead, the PPO loss: train.ppo_loss forward plus autograd's backward to values, log_prob
+and entropy against train.ppo_loss_kernel (ha_ppo_loss) on the same tensors at 64, 262,144 and 2^22 rows,
+beside the bytes floor (40 B a row at the 6.29 TB/s copy ceiling), and one ppo_update epoch with
+loss="torch" and loss="kernel" (DeviceAdam) at 32 x 2 (envs_per_batch 1) and 256 x 4,096 (envs_per_batch
+1,024).  Both paths run in this process.
 """
 import argparse
 import copy
@@ -152,7 +158,7 @@ def measure_update(m, K, n, per, reps):
     return measure_update_with(m, torch.optim.Adam(m.parameters(), lr=1e-5, eps=1e-5), K, n, per, reps)
 
 
-def measure_update_with(m, opt, K, n, per, reps):
+def measure_update_with(m, opt, K, n, per, reps, **kw):
     buf = RolloutBuffer(K, n, DEV)
     g = torch.Generator(device=DEV).manual_seed(2)
     for name in ("observations", "actions", "rewards", "values", "advantages", "returns", "h_pi", "c_pi", "h_vf", "c_vf"):
@@ -160,7 +166,7 @@ def measure_update_with(m, opt, K, n, per, reps):
         t.copy_(torch.randn(t.shape, device=DEV, generator=g) * 0.5)
     buf.log_probs.fill_(-1.0)
     buf.episode_starts.copy_((torch.rand((K, n), device=DEV, generator=g) < 0.004).to(torch.uint8))
-    us = median_us(lambda: train.ppo_update(m, opt, buf, n_epochs=1, envs_per_batch=per), reps, 1)
+    us = median_us(lambda: train.ppo_update(m, opt, buf, n_epochs=1, envs_per_batch=per, **kw), reps, 1)
     return dict(ppo_update_epoch_us=round(us, 1), K=K, n_envs=n, envs_per_batch=per, minibatches=-(-n // per), update_reps=reps)
 
 
@@ -235,6 +241,52 @@ def measure_optimizer(shapes, reps):
     return lines
 
 
+LOSS_ROWS = (64, 262144, 1 << 22)
+LOSS_UPDATES = ((32, 2, 1), (256, 4096, 1024))   # K, n, envs_per_batch
+BYTES_LOSS = 40                                  # per row: six f32 read (a seventh with a value clip), three f32 written, each once
+
+
+def measure_loss(reps):
+    """--loss: the loss alone per row count (forward plus the backward to the heads' three outputs), then
+    one ppo_update epoch per shape with either loss path."""
+    hyper = (0.3, 1e-5, 0.5)
+    lines = []
+    g = torch.Generator(device=DEV).manual_seed(5)
+    for rows in LOSS_ROWS:
+        t = [torch.randn(rows, device=DEV, generator=g) for _ in range(6)]
+        t[1] = t[3] + 0.3 * t[1]                  # log_prob around old_log_prob: ratios on both sides of the clip
+        leaves = [x.clone().requires_grad_() for x in t[:3]]
+
+        def torch_path():
+            loss, _ = train.ppo_loss(*leaves, *t[3:], *hyper)
+            torch.autograd.grad(loss, leaves)
+
+        r = dict(mode="loss", rows=rows, reps=reps, device=torch.cuda.get_device_name(0))
+        r["loss_torch_us"] = round(median_us(torch_path, reps, 3), 1)
+        r["loss_kernel_us"] = round(median_us(lambda: train.ppo_loss_kernel(*t, *hyper), reps, 3), 1)
+        r["loss_kernel_no_norm_us"] = round(median_us(lambda: train.ppo_loss_kernel(*t, *hyper, False), reps, 3), 1)
+        r["loss_speedup"] = round(r["loss_torch_us"] / r["loss_kernel_us"], 2)
+        r["loss_floor_bytes_us"] = round(rows * BYTES_LOSS / COPY_CEILING * 1e6, 2)
+        r["loss_kernel_frac_of_bytes_floor"] = round(r["loss_floor_bytes_us"] / r["loss_kernel_us"], 3)
+        lines.append(r)
+        del t, leaves
+        torch.cuda.empty_cache()
+    m = module(np.random.default_rng(0))
+    for K, n, per in LOSS_UPDATES:
+        u = dict(mode="loss_update", optimizer="device_adam", device=torch.cuda.get_device_name(0))
+        for loss in train.LOSSES:
+            mm = copy.deepcopy(m)
+            res = measure_update_with(mm, train.DeviceAdam(mm.parameters(), lr=1e-5, eps=1e-5), K, n, per, reps,
+                                      loss=loss)
+            u[f"ppo_update_epoch_loss_{loss}_us"] = res.pop("ppo_update_epoch_us")
+            u.update(res)
+            del mm
+            torch.cuda.empty_cache()
+        u["loss_kernel_speedup"] = round(u["ppo_update_epoch_loss_torch_us"] / u["ppo_update_epoch_loss_kernel_us"], 3)
+        lines.append(u)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="*", default=["256,4096", "256,16384", "32,2"])
@@ -243,12 +295,17 @@ def main():
     ap.add_argument("--weight-grads", choices=("torch", "kernel", "both"), default="torch")
     ap.add_argument("--optimizer", action="store_true",
                     help="time the clip + optimizer step and the policy refresh against their baselines instead")
+    ap.add_argument("--loss", action="store_true",
+                    help="time ppo_loss_kernel against ppo_loss, alone and inside ppo_update, instead")
     a = ap.parse_args()
     lines = []
-    if a.optimizer:
+    if a.loss:
+        lines = [json.dumps(r) for r in measure_loss(a.reps)]
+        print("\n".join(lines), flush=True)
+    elif a.optimizer:
         lines = [json.dumps(r) for r in measure_optimizer([tuple(int(v) for v in s.split(",")) for s in a.shapes], a.reps)]
         print("\n".join(lines), flush=True)
-    for k, s in enumerate([] if a.optimizer else a.shapes):
+    for k, s in enumerate([] if a.optimizer or a.loss else a.shapes):
         L, B = (int(v) for v in s.split(","))
         r, m = measure(L, B, a.reps, a.weight_grads)
         if k == 0 and a.weight_grads != "kernel":
