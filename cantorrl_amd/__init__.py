@@ -18,6 +18,10 @@ reference's Python interface on top:
   launch (agent.py): a training iteration without a host round trip
 * `ppo_loss_kernel` -- RecurrentPPO.train's loss, its statistics and its gradients with respect to
   values, log_prob and entropy as kernels with an arithmetic contract (train.py, ha_ppo_loss)
+* `ppo_heads`, `ppo_heads_forward`, `ppo_heads_backward`, `heads_weight_grads` -- the part of
+  evaluate_actions after the LSTMs (MLPs, action and value heads, log-probability, entropy) and its
+  backward down to the LSTMs' outputs as kernels under the step kernel's contract (train.py,
+  ha_ppo_heads_forward / _backward); `RecurrentPPOModule(heads="kernel")` routes through it
 """
 __version__ = "0.1.0"
 
@@ -39,7 +43,7 @@ def __getattr__(name):
         from .collect import RolloutCollector
         return RolloutCollector
     if name in ("lstm_sequence", "lstm_sequence_pair", "RecurrentPPOModule", "ppo_update", "DeviceAdam",
-                "ppo_loss_kernel"):
+                "ppo_loss_kernel", "ppo_heads", "ppo_heads_forward", "ppo_heads_backward", "heads_weight_grads"):
         from . import train
         return getattr(train, name)
     raise AttributeError(name)

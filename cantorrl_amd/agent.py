@@ -123,6 +123,11 @@ SIG = {
     "ha_ppo_loss_workspace_bytes": (ctypes.c_size_t, [_i64]),
     "ha_ppo_loss": (_i32, [_i64, _vp, _vp, _vp, _vp]),
     "ha_host_ppo_loss": (_i32, [_i64, _vp, _vp]),
+    "ha_ppo_heads_workspace_bytes": (ctypes.c_size_t, [_i64]),
+    "ha_ppo_heads_forward": (_i32, [_i64, _vp, _vp, _vp, _vp]),
+    "ha_ppo_heads_backward": (_i32, [_i64, _vp, _vp, _vp, _vp]),
+    "ha_host_ppo_heads_forward": (_i32, [_i64, _vp, _vp]),
+    "ha_host_ppo_heads_backward": (_i32, [_i64, _vp, _vp]),
 }
 EXPORTS = list(SIG)
 

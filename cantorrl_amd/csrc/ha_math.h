@@ -1,6 +1,6 @@
 // ha_math.h -- the scalar arithmetic of the RecurrentPPO actor (include/hedge_actor.h,
-// "Arithmetic contract"), its rollout policy (sampling, log-probability), GAE, the optimizer step and
-// the PPO loss, shared by the HIP kernels (__device__) and the ha_host_* entry points (__host__):
+// "Arithmetic contract"), its rollout policy (sampling, log-probability), GAE, the optimizer step, the
+// PPO loss and the PPO heads, shared by the HIP kernels (__device__) and the ha_host_* entry points (__host__):
 // one implementation, so the two agree bit for bit.  The library is compiled with
 // -ffp-contract=off; f64 + - * / are IEEE on both sides and he::exp_k is host / device identical.
 #pragma once
@@ -102,6 +102,16 @@ HE_HD float squash_action(float mean, bool tanh_squash) {
 // std = f32(exp(f64(log_std)))
 HE_HD float policy_std(float log_std) { return (float)he::exp_k((double)log_std); }
 
+// Contract P6's z_j and the term of action j in the log-probability (the loop of sample_action and of
+// heads_log_prob): one f64 rounding per line
+HE_HD double gauss_z(float a, float mean, float stdv) { return ((double)a - (double)mean) / (double)stdv; }
+HE_HD double log_prob_term(double z, float log_std) {
+    const double zz = z * z;
+    const double t = -0.5 * zz;
+    const double u = t - (double)log_std;
+    return u - 0.9189385332046727;
+}
+
 // Contract steps 4-6: the diagonal-Gaussian sample of env g at step_index, its clipped form and
 // its log-probability.  One Philox block per (seed, step_index, g): nothing depends on how the
 // envs are split over calls.
@@ -125,12 +135,7 @@ HE_HD void sample_action(const float* mean, const float* log_std, const float* s
     for (int j = 0; j < kAct; ++j) {
         a[j] = deterministic ? mean[j] : fmaf(stdv[j], eps[j], mean[j]);
         env_a[j] = he::np_clipf(a[j], -1.0f, 1.0f);
-        const double z = ((double)a[j] - (double)mean[j]) / (double)stdv[j];
-        const double zz = z * z;
-        const double t = -0.5 * zz;
-        const double u = t - (double)log_std[j];
-        const double v = u - 0.9189385332046727;
-        lp = lp + v;
+        lp = lp + log_prob_term(gauss_z(a[j], mean[j], stdv[j]), log_std[j]);
     }
     *log_prob = (float)lp;
 }
@@ -269,6 +274,46 @@ HE_HD void loss_stats(const double* tot, double mean, double sd, const LossConst
     stats[5] = (float)(tot[4] / k.n);
     stats[6] = (float)mean;
     stats[7] = (float)sd;
+}
+
+// ---------------------------------------------------------------- the PPO heads (ha_ppo_heads_*)
+// Contract H2: the log-probability of the stored action a[2] under Normal(mean, std), P6's sum
+HE_HD float heads_log_prob(const float* a, const float* mean, const float* log_std, const float* stdv) {
+    double lp = 0.0;
+    for (int j = 0; j < kAct; ++j) lp = lp + log_prob_term(gauss_z(a[j], mean[j], stdv[j]), log_std[j]);
+    return (float)lp;
+}
+
+// Contract H3: the entropy of the diagonal Gaussian, the same for every row
+HE_HD float heads_entropy(const float* log_std) {
+    double e = 0.0;
+    for (int j = 0; j < kAct; ++j) {
+        const double t = (0.5 + 0.9189385332046727) + (double)log_std[j];
+        e = e + t;
+    }
+    return (float)e;
+}
+
+// Contract H4: the gradient of mean[j] from the row's d_log_prob and z_j
+HE_HD float heads_d_mean(float d_lp, double z, float stdv) {
+    const double q = z / (double)stdv;
+    return (float)((double)d_lp * q);
+}
+
+// Contract H6's term of one row for action j
+HE_HD double heads_lsd_term(float d_lp, double z, float d_ent) {
+    const double zz = z * z;
+    const double zm = zz - 1.0;
+    const double p = (double)d_lp * zm;
+    return p + (double)d_ent;
+}
+
+// Contract H5: the gradient of a pre-activation from that of the activation a = act(z)
+HE_HD float act_backward(float d_a, float a, bool relu) {
+    if (relu) return a > 0.0f ? d_a : 0.0f;
+    const float aa = a * a;
+    const float om = 1.0f - aa;
+    return d_a * om;
 }
 
 }  // namespace ha

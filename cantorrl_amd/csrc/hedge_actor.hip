@@ -27,7 +27,8 @@
 // one thread per env over [K][n] arrays.  lstm_seq_fwd_kernel / lstm_seq_bwd_kernel (the PPO update's
 // LSTM over a stored sequence, forward and backward) and lstm_wgrad_kernel / lstm_wgrad_reduce_kernel
 // (its weight gradients), policy_pack_kernel (ha_policy_refresh), opt_norm_kernel / opt_adam_kernel
-// (ha_adam_step) and the four loss_*_kernel (ha_ppo_loss) are described where they stand.
+// (ha_adam_step), the four loss_*_kernel (ha_ppo_loss) and the four heads_*_kernel (ha_ppo_heads_forward /
+// _backward) are described where they stand.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -1574,6 +1575,497 @@ double loss_sum_host(int64_t n, F term) {
     return total;
 }
 
+// ---------------------------------------------------------------- the PPO heads (contract H1-H6)
+// heads_pack_kernel / heads_fwd_kernel / heads_bwd_kernel / heads_lsd_kernel (ha_ppo_heads_forward /
+// _backward).  A tile is 64 rows: two halves of 32, the MFMA's columns.  The four waves of a workgroup are
+// (32-output slice, row half) pairs, and a workgroup keeps the A fragments of its slices resident over all
+// the tiles it walks, read once from the workspace: 64 + 32 floats a lane in the backward's registers;
+// in the forward, whose f64 activations need the registers, 32 there and layer 1's in LDS.
+//   pack      the weights change with every optimizer step: W1, W2 in mlp_slice's fragment order, their
+//             transposes in the same order (wt[o][s][lane] = W[2 s + (lane >> 5)][32 o + (lane & 31)]), and
+//             log_std with std = policy_std(log_std).
+//   forward   grid (groups of tiles, 2), y = actor / critic.  h of the tile to LDS as [half][k][row] at
+//             kLd; layer 1 and layer 2 one accumulator each from the bias (mlp_slice's chain), a1 and a2
+//             to LDS for the next product (over h, which layer 1 has read by then) and to HBM as 16-byte
+//             lines from the accumulator's own layout; the head chain and H2 / H3 on the VALU, one lane
+//             pair a row.  Layer 1's fragments stay in LDS, layer 2's in registers.
+//   backward  grid (blocks of HA_LOSS_BLOCK rows, 2): a workgroup walks the 16 tiles of its block.  H4 and
+//             H6's terms one lane a row (the terms wait in LDS for the block's tree); d_a2, d_z2 on the
+//             VALU; d_z2, d_z1 through LDS as [half][u][row], the B operand of W2^T and W1^T with u as k,
+//             accumulators from +0; d_h as 16-byte lines.  The actor's workgroup ends with L1's lane sums
+//             and tree over its block and writes the two s_b; heads_lsd_kernel adds them in block order.
+constexpr int kHRows = 64;                                  // rows of a tile
+constexpr int kHTiles = HA_LOSS_BLOCK / kHRows;            // tiles of one block of L1
+constexpr size_t kHw1p = 0, kHw2p = kHw1p + (size_t)kMlp * kHid, kHw1t = kHw2p + (size_t)kMlp * kMlp;
+constexpr size_t kHw2t = kHw1t + (size_t)kMlp * kHid, kHeadsNetFloats = kHw2t + (size_t)kMlp * kMlp;
+constexpr size_t kHls = 2 * kHeadsNetFloats, kHpart = kHls + 4;   // log_std[2], std[2]; then f64 [2][blocks]
+static_assert(kHeadsNetFloats % 4 == 0 && (kHpart * sizeof(float)) % 16 == 0, "aligned sections");
+static_assert(HA_LOSS_BLOCK % kHRows == 0 && kHRows == 2 * kTile, "whole tiles a block, two MFMA halves a tile");
+
+struct HeadsNetW {
+    const float *w1, *b1, *w2, *b2, *w3, *b3;
+    int n_out;
+};
+
+inline HeadsNetW heads_net(const ha_ppo_heads_weights* w, bool critic) {
+    return critic ? HeadsNetW{w->v1, w->vb1, w->v2, w->vb2, w->v3, w->vb3, 1}
+                  : HeadsNetW{w->w1, w->b1, w->w2, w->b2, w->w3, w->b3, kAct};
+}
+
+struct HeadsPackParams {
+    const float* w1[2];
+    const float* w2[2];
+    const float* log_std;
+    float* ws;
+};
+
+struct HeadsFwdParams {
+    int64_t n;
+    int32_t relu, tiles_per_wg;
+    ha_ppo_heads_fwd io;
+    HeadsNetW net[2];
+    const float* ws;
+};
+
+struct HeadsBwdParams {
+    int64_t n;
+    int32_t relu, nb;
+    ha_ppo_heads_bwd io;
+    HeadsNetW net[2];
+    const float* ws;
+    double* part;   // [2][nb]
+};
+
+// grid (blocks, 2): one network's four sections; the first thread pair of the grid adds log_std, std
+__global__ __launch_bounds__(256) void heads_pack_kernel(const HeadsPackParams p) {
+    const bool critic = blockIdx.y != 0;
+    const float* __restrict__ w1 = critic ? p.w1[1] : p.w1[0];
+    const float* __restrict__ w2 = critic ? p.w2[1] : p.w2[0];
+    float* dst = p.ws + (critic ? kHeadsNetFloats : 0);
+    for (unsigned idx = blockIdx.x * 256 + threadIdx.x; idx < kHeadsNetFloats; idx += gridDim.x * 256) {
+        const int l = idx & 63, m = l & 31, hi = l >> 5;
+        float v;
+        if (idx < kHw2p) {          // [2][64][64]
+            const int s = (idx >> 6) & 63, rt = idx >> 12;
+            v = w1[(rt * 32 + m) * kHid + 2 * s + hi];
+        } else if (idx < kHw1t) {   // [2][32][64]
+            const unsigned i = idx - kHw2p;
+            const int s = (i >> 6) & 31, rt = i >> 11;
+            v = w2[(rt * 32 + m) * kMlp + 2 * s + hi];
+        } else if (idx < kHw2t) {   // [4][32][64]
+            const unsigned i = idx - kHw1t;
+            const int s = (i >> 6) & 31, ot = i >> 11;
+            v = w1[(2 * s + hi) * kHid + ot * 32 + m];
+        } else {                    // [2][32][64]
+            const unsigned i = idx - kHw2t;
+            const int s = (i >> 6) & 31, ot = i >> 11;
+            v = w2[(2 * s + hi) * kMlp + ot * 32 + m];
+        }
+        dst[idx] = v;
+    }
+    if (!critic && blockIdx.x == 0 && threadIdx.x < kAct) {
+        const float ls = p.log_std[threadIdx.x];
+        p.ws[kHls + threadIdx.x] = ls;
+        p.ws[kHls + kAct + threadIdx.x] = policy_std(ls);
+    }
+}
+
+struct HeadsFwdTile {
+    float h[2][kHid][kLd];       // 33,792 B; once layer 1 has read h, a2 takes its rows 0 .. 63 and a1 its rows 64 .. 127
+    float w1[2][kHid / 2][64];   // 32,768 B: layer 1's A fragments, both slices
+    float w3[kAct * kMlp];
+    float b1[kMlp], b2[kMlp];    // the small tensors once, not a pointer each through the tile loop
+    float b3[4], ls[4];          // b3; log_std[2], std[2]
+};
+
+// the accumulator's registers from 16 consecutive-by-four biases: register 4 q + j is output 8 q + 4 hi + j
+__device__ __forceinline__ void heads_bias(const float* b, int hi, float* out) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float4 v = *(const float4*)(b + 8 * q + 4 * hi);
+        out[4 * q + 0] = v.x; out[4 * q + 1] = v.y; out[4 * q + 2] = v.z; out[4 * q + 3] = v.w;
+    }
+}
+
+// act(acc) of one 32 x 32 product to LDS as out[unit][col] and, where the row exists, to HBM as four
+// 16-byte lines of row `dst` (the row's 64 floats; o0 the slice's first unit)
+__device__ __forceinline__ void heads_act_store(const f32x16& acc, float (*out)[kLd], float* dst, int o0, int col,
+                                                int hi, bool relu) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) out[o0 + (r & 3) + 8 * (r >> 2) + 4 * hi][col] = acc[r];
+    // the lane's own 16 values back from LDS, four at a time in a rolled loop: the f64 temporaries of four
+    // activations, not of sixteen, stand beside the resident fragments
+#pragma unroll 1
+    for (int q = 0; q < 4; ++q) {
+        const int u = o0 + 8 * q + 4 * hi;
+        float o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            o[j] = mlp_act(out[u + j][col], relu);
+            out[u + j][col] = o[j];
+        }
+        if (dst) *(float4*)(dst + u) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+__global__ __launch_bounds__(kThreads, 2) void heads_fwd_kernel(const HeadsFwdParams p) {
+    __shared__ HeadsFwdTile t;
+    const int tid = threadIdx.x;
+    const bool critic = blockIdx.y != 0;
+    const bool relu = p.relu != 0;
+    const HeadsNetW nw = critic ? p.net[1] : p.net[0];
+    const float* __restrict__ ws = p.ws + (critic ? kHeadsNetFloats : 0);
+    const float* __restrict__ h = critic ? p.io.h_vf : p.io.h_pi;
+    float* a1o = critic ? p.io.a1_vf : p.io.a1_pi;
+    float* a2o = critic ? p.io.a2_vf : p.io.a2_pi;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int col = lane & 31, hi = lane >> 5;
+    const int rt = wave & 1, rh = wave >> 1;   // output slice, row half
+
+    // ---- the wave's A fragments and biases, resident over its tiles
+    float w2r[kMlp / 2];
+    {
+        const float* w2p = ws + kHw2p + (size_t)rt * (kMlp / 2) * 64 + lane;
+#pragma unroll
+        for (int s = 0; s < kMlp / 2; ++s) w2r[s] = w2p[s * 64];
+        for (int i = tid; i < kMlp * kHid; i += kThreads) (&t.w1[0][0][0])[i] = ws[kHw1p + i];
+    }
+    if (tid < nw.n_out * kMlp) t.w3[tid] = nw.w3[tid];
+    if (tid < kMlp) t.b1[tid] = nw.b1[tid], t.b2[tid] = nw.b2[tid];
+    if (tid < nw.n_out) t.b3[tid] = nw.b3[tid];
+    if (tid < 4) t.ls[tid] = p.ws[kHls + tid];
+
+    const int n = (int)p.n;   // at most 2^22 rows: 32-bit row arithmetic
+    const int ntiles = (n + kHRows - 1) / kHRows;
+    int tile = (int)blockIdx.x * p.tiles_per_wg;
+    const int end = tile + p.tiles_per_wg < ntiles ? tile + p.tiles_per_wg : ntiles;
+    for (; tile < end; ++tile) {
+        const int r0 = tile * kHRows;
+        // ---- stage h: a wave loads 8 rows x 128 B a pass; rows past n are zero columns
+#pragma unroll 1
+        for (int it = 0; it < 8; ++it) {
+            const int row = (tid & 7) + 8 * it, k4 = ((tid >> 3) & 7) + 8 * wave;
+            float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (r0 + row < n) v = *(const float4*)(h + (size_t)(r0 + row) * kHid + 4 * k4);
+            float(*dst)[kLd] = t.h[row >> 5];
+            dst[4 * k4 + 0][row & 31] = v.x;
+            dst[4 * k4 + 1][row & 31] = v.y;
+            dst[4 * k4 + 2][row & 31] = v.z;
+            dst[4 * k4 + 3][row & 31] = v.w;
+        }
+        __syncthreads();
+        const int r = r0 + rh * 32 + col;
+        const bool valid = r < n;
+        // ---- layer 1
+        {
+            float bias[16];
+            heads_bias(t.b1 + rt * 32, hi, bias);
+            f32x16 acc;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] = bias[i];
+#pragma unroll
+            for (int s = 0; s < kHid / 2; ++s)
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(t.w1[rt][s][lane], t.h[rh][2 * s + hi][col], acc, 0, 0, 0);
+            __syncthreads();   // every wave has read h
+            heads_act_store(acc, t.h[rh] + kMlp, valid ? a1o + (size_t)r * kMlp : nullptr, rt * 32, col, hi, relu);
+        }
+        __syncthreads();
+        // ---- layer 2
+        {
+            float bias[16];
+            heads_bias(t.b2 + rt * 32, hi, bias);
+            f32x16 acc;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] = bias[i];
+#pragma unroll
+            for (int s = 0; s < kMlp / 2; ++s)
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w2r[s], t.h[rh][kMlp + 2 * s + hi][col], acc, 0, 0, 0);
+            heads_act_store(acc, t.h[rh], valid ? a2o + (size_t)r * kMlp : nullptr, rt * 32, col, hi, relu);
+        }
+        __syncthreads();
+        // ---- the head: lane pair (2 el, 2 el + 1) = the two outputs of row el (waves 0 and 1)
+        if (tid < kHRows * kAct) {
+            const int el = tid >> 1, j = tid & 1;
+            const int re = r0 + el;
+            const float(*a2)[kLd] = t.h[el >> 5];
+            if (critic) {
+                if (j == 0) {
+                    const float v = head_chain(t.w3, t.b3[0], a2, el & 31);
+                    if (re < n) p.io.values[re] = v;
+                }
+            } else {
+                const float m = head_chain(t.w3 + j * kMlp, t.b3[j], a2, el & 31);
+                const float mo = __shfl_xor(m, 1);
+                if (j == 0 && re < n) {
+                    const float mean[kAct] = {m, mo};
+                    const float2 av = *(const float2*)(p.io.actions + (size_t)re * kAct);
+                    const float a[kAct] = {av.x, av.y};
+                    const float* ls = t.ls;
+                    *(float2*)(p.io.mean + (size_t)re * kAct) = make_float2(m, mo);
+                    p.io.log_prob[re] = heads_log_prob(a, mean, ls, ls + kAct);
+                    p.io.entropy[re] = heads_entropy(ls);
+                }
+            }
+        }
+        __syncthreads();   // a2 is read before the next tile's h lands on it
+    }
+}
+
+struct HeadsBwdTile {
+    float dz2[2][kMlp][kLd];   // 16,896 B
+    float dz1[2][kMlp][kLd];   // 16,896 B
+    float dout[kHRows][kAct];
+    float w3[kAct * kMlp];
+    double term[kAct][HA_LOSS_BLOCK];   // 16,384 B: H6's terms of the block's rows
+    double q[kAct][kLossLanes];
+};
+
+__global__ __launch_bounds__(kThreads, 2) void heads_bwd_kernel(const HeadsBwdParams p) {
+    __shared__ HeadsBwdTile t;
+    const int tid = threadIdx.x;
+    const bool critic = blockIdx.y != 0;
+    const bool relu = p.relu != 0;
+    const HeadsNetW nw = critic ? p.net[1] : p.net[0];
+    const float* __restrict__ ws = p.ws + (critic ? kHeadsNetFloats : 0);
+    const float* __restrict__ a1i = critic ? p.io.a1_vf : p.io.a1_pi;
+    const float* __restrict__ a2i = critic ? p.io.a2_vf : p.io.a2_pi;
+    float* dz1o = critic ? p.io.d_z1_vf : p.io.d_z1_pi;
+    float* dz2o = critic ? p.io.d_z2_vf : p.io.d_z2_pi;
+    float* dho = critic ? p.io.d_h_vf : p.io.d_h_pi;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int col = lane & 31, hi = lane >> 5;
+    const int ot = wave & 1, rh = wave >> 1;   // W2^T: output slice ot; W1^T: slices 2 ot, 2 ot + 1
+    const int n_out = nw.n_out;
+
+    float w2r[kMlp / 2], w1r[2][kMlp / 2];
+    {
+        const float* w2t = ws + kHw2t + (size_t)ot * (kMlp / 2) * 64 + lane;
+        const float* w1t = ws + kHw1t + (size_t)(2 * ot) * (kMlp / 2) * 64 + lane;
+#pragma unroll
+        for (int s = 0; s < kMlp / 2; ++s) {
+            w2r[s] = w2t[s * 64];
+            w1r[0][s] = w1t[s * 64];
+            w1r[1][s] = w1t[(kMlp / 2 + s) * 64];
+        }
+    }
+    if (tid < n_out * kMlp) t.w3[tid] = nw.w3[tid];
+    else if (tid < kAct * kMlp) t.w3[tid] = 0.0f;
+
+    const int64_t b0 = (int64_t)blockIdx.x * HA_LOSS_BLOCK;
+    for (int ti = 0; ti < kHTiles; ++ti) {
+        const int64_t r0 = b0 + (int64_t)ti * kHRows;
+        if (r0 >= p.n) break;
+        // ---- H4 and H6's terms: one lane a row
+        if (tid < kHRows) {
+            const int64_t re = r0 + tid;
+            float d0 = 0.0f, d1 = 0.0f;
+            if (critic) {
+                if (re < p.n) d0 = p.io.d_values[re];
+            } else {
+                double t0 = 0.0, t1 = 0.0;
+                if (re < p.n) {
+                    const float* ls = p.ws + kHls;
+                    const float2 av = *(const float2*)(p.io.actions + re * kAct);
+                    const float2 mv = *(const float2*)(p.io.mean + re * kAct);
+                    const float dlp = p.io.d_log_prob[re], den = p.io.d_entropy[re];
+                    const double z0 = gauss_z(av.x, mv.x, ls[kAct]), z1 = gauss_z(av.y, mv.y, ls[kAct + 1]);
+                    d0 = heads_d_mean(dlp, z0, ls[kAct]);
+                    d1 = heads_d_mean(dlp, z1, ls[kAct + 1]);
+                    t0 = heads_lsd_term(dlp, z0, den);
+                    t1 = heads_lsd_term(dlp, z1, den);
+                    *(float2*)(p.io.d_mean + re * kAct) = make_float2(d0, d1);
+                }
+                t.term[0][ti * kHRows + tid] = t0;
+                t.term[1][ti * kHRows + tid] = t1;
+            }
+            t.dout[tid][0] = d0;
+            t.dout[tid][1] = d1;
+        }
+        __syncthreads();
+        // ---- d_a2 and d_z2 on the VALU: a wave takes 16 rows x 64 B of a2 a pass
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const int row = (lane & 15) + 16 * it, k4 = (lane >> 4) + 4 * wave;
+            const int64_t re = r0 + row;
+            float4 av = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (re < p.n) av = *(const float4*)(a2i + re * kMlp + 4 * k4);
+            const float a[4] = {av.x, av.y, av.z, av.w};
+            float d[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float s = 0.0f;
+                for (int o = 0; o < n_out; ++o) s = fmaf(t.dout[row][o], t.w3[o * kMlp + 4 * k4 + j], s);
+                d[j] = act_backward(s, a[j], relu);
+                t.dz2[row >> 5][4 * k4 + j][row & 31] = d[j];
+            }
+            if (re < p.n) *(float4*)(dz2o + re * kMlp + 4 * k4) = make_float4(d[0], d[1], d[2], d[3]);
+        }
+        __syncthreads();
+        const int64_t r = r0 + rh * 32 + col;
+        const bool valid = r < p.n;
+        // ---- d_a1 = W2^T d_z2, d_z1
+        {
+            f32x16 acc;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
+#pragma unroll
+            for (int s = 0; s < kMlp / 2; ++s)
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w2r[s], t.dz2[rh][2 * s + hi][col], acc, 0, 0, 0);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int u = ot * 32 + 8 * q + 4 * hi;
+                float4 av = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (valid) av = *(const float4*)(a1i + r * kMlp + u);
+                const float a[4] = {av.x, av.y, av.z, av.w};
+                float d[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    d[j] = act_backward(acc[4 * q + j], a[j], relu);
+                    t.dz1[rh][u + j][col] = d[j];
+                }
+                if (valid) *(float4*)(dz1o + r * kMlp + u) = make_float4(d[0], d[1], d[2], d[3]);
+            }
+        }
+        __syncthreads();
+        // ---- d_h = W1^T d_z1: two output slices a wave
+        {
+            f32x16 acc0, acc1;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = 0.0f;
+#pragma unroll
+            for (int s = 0; s < kMlp / 2; ++s) {
+                const float b = t.dz1[rh][2 * s + hi][col];
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w1r[0][s], b, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(w1r[1][s], b, acc1, 0, 0, 0);
+            }
+            if (valid) {
+                float* dst = dho + r * kHid + (2 * ot) * 32 + 4 * hi;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    *(float4*)(dst + 8 * q) = make_float4(acc0[4 * q], acc0[4 * q + 1], acc0[4 * q + 2], acc0[4 * q + 3]);
+                    *(float4*)(dst + 32 + 8 * q) = make_float4(acc1[4 * q], acc1[4 * q + 1], acc1[4 * q + 2], acc1[4 * q + 3]);
+                }
+            }
+        }
+    }
+    if (critic) return;
+    // ---- H6: L1's lane sums and tree over the block's terms
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kAct; ++j) {
+        double s = 0.0;
+#pragma unroll
+        for (int m = 0; m < kLossPerLane; ++m) {
+            const int i = m * kLossLanes + tid;
+            s = s + (b0 + i < p.n ? t.term[j][i] : 0.0);
+        }
+        t.q[j][tid] = s;
+    }
+    loss_tree<kAct>(t.q, tid);
+    if (tid < kAct) p.part[(int64_t)tid * p.nb + blockIdx.x] = t.q[tid][0];
+}
+
+// one workgroup: the blocks' sums of H6 in block order, rounded once
+__global__ __launch_bounds__(kLossLanes) void heads_lsd_kernel(const double* __restrict__ part, int nb, float* d_log_std) {
+    __shared__ double stage[kAct * kLossStage];
+    __shared__ double tot[kAct];
+    const int tid = threadIdx.x;
+    loss_totals<kAct>(part, nb, tid, stage, tot);
+    if (tid < kAct) d_log_std[tid] = (float)tot[tid];
+}
+
+// The checks of the four ha_ppo_heads entry points: m16 / m8 are the alignment masks of the [R][128],
+// [R][64] and weight arrays and of the [R][2] arrays (3 on the host).  ptrs16 / ptrs8 / ptrs4 end at n16 ...
+ha_status check_heads_rows(int64_t n) {
+    char m[200];
+    if (n < 1 || n > (int64_t)HA_LOSS_BLOCK * HA_LOSS_MAX_BLOCKS) {
+        snprintf(m, sizeof m, "n_rows = %lld: 1 to %lld rows a call (%d blocks of %d)", (long long)n,
+                 (long long)HA_LOSS_BLOCK * HA_LOSS_MAX_BLOCKS, HA_LOSS_MAX_BLOCKS, HA_LOSS_BLOCK);
+        return fail_to(nullptr, HE_ESHAPE, m);
+    }
+    return HE_OK;
+}
+
+ha_status check_heads(int64_t n, const ha_ppo_heads_weights* w, const void* io, uintptr_t m16, uintptr_t m8,
+                      const void* const* p16, int n16, const void* const* p8, int n8, const void* const* p4, int n4) {
+    const ha_status st = check_heads_rows(n);
+    if (st != HE_OK) return st;
+    if (!w || !io) return fail_to(nullptr, HE_EINVAL, "weights or io is NULL");
+    if (w->activation != HA_ACT_TANH && w->activation != HA_ACT_RELU) return fail_to(nullptr, HE_EINVAL, "unknown activation");
+    const void* big[] = {w->w1, w->b1, w->w2, w->b2, w->w3, w->v1, w->vb1, w->v2, w->vb2, w->v3};
+    const void* small[] = {w->b3, w->log_std, w->vb3};
+    for (const void* q : big)
+        if (bad_ptr(q, m16)) return fail_to(nullptr, HE_EINVAL, "a weight tensor is NULL or not 16-byte aligned");
+    for (const void* q : small)
+        if (bad_ptr(q, 3u)) return fail_to(nullptr, HE_EINVAL, "b3, vb3 or log_std is NULL or not 4-byte aligned");
+    for (int i = 0; i < n16; ++i)
+        if (bad_ptr(p16[i], m16)) return fail_to(nullptr, HE_EINVAL, "a [R][128] or [R][64] array of io is NULL or not 16-byte aligned");
+    for (int i = 0; i < n8; ++i)
+        if (bad_ptr(p8[i], m8)) return fail_to(nullptr, HE_EINVAL, "a [R][2] array of io is NULL or not 8-byte aligned");
+    for (int i = 0; i < n4; ++i)
+        if (bad_ptr(p4[i], 3u)) return fail_to(nullptr, HE_EINVAL, "a per-row array of io is NULL or not 4-byte aligned");
+    return HE_OK;
+}
+
+ha_status check_heads_fwd(int64_t n, const ha_ppo_heads_weights* w, const ha_ppo_heads_fwd* io, uintptr_t m16, uintptr_t m8) {
+    if (!io) return check_heads(n, w, nullptr, m16, m8, nullptr, 0, nullptr, 0, nullptr, 0);
+    const void* p16[] = {io->h_pi, io->h_vf, io->a1_pi, io->a2_pi, io->a1_vf, io->a2_vf};
+    const void* p8[] = {io->actions, io->mean};
+    const void* p4[] = {io->values, io->log_prob, io->entropy};
+    return check_heads(n, w, io, m16, m8, p16, 6, p8, 2, p4, 3);
+}
+
+ha_status check_heads_bwd(int64_t n, const ha_ppo_heads_weights* w, const ha_ppo_heads_bwd* io, uintptr_t m16, uintptr_t m8) {
+    if (!io) return check_heads(n, w, nullptr, m16, m8, nullptr, 0, nullptr, 0, nullptr, 0);
+    const void* p16[] = {io->a1_pi, io->a2_pi, io->a1_vf, io->a2_vf, io->d_h_pi, io->d_h_vf,
+                         io->d_z1_pi, io->d_z2_pi, io->d_z1_vf, io->d_z2_vf};
+    const void* p8[] = {io->actions, io->mean, io->d_mean};
+    const void* p4[] = {io->d_values, io->d_log_prob, io->d_entropy, io->d_log_std};
+    return check_heads(n, w, io, m16, m8, p16, 10, p8, 3, p4, 4);
+}
+
+ha_status heads_pack(const ha_ppo_heads_weights* w, void* workspace, void* stream) {
+    HeadsPackParams pp;
+    pp.w1[0] = w->w1, pp.w1[1] = w->v1, pp.w2[0] = w->w2, pp.w2[1] = w->v2;
+    pp.log_std = w->log_std;
+    pp.ws = (float*)workspace;
+    return launch(nullptr, heads_pack_kernel, dim3(24, 2), dim3(256), stream, "heads_pack_kernel", pp);
+}
+
+// H1 for one network and row on the host: the two layers into a1, a2
+void host_heads_mlp(const HeadsNetW& w, const float* h, bool relu, float* a1, float* a2) {
+    for (int j = 0; j < kMlp; ++j) {
+        float acc = w.b1[j];
+        for (int k = 0; k < kHid; ++k) acc = fmaf(w.w1[j * kHid + k], h[k], acc);
+        a1[j] = mlp_act(acc, relu);
+    }
+    for (int j = 0; j < kMlp; ++j) {
+        float acc = w.b2[j];
+        for (int k = 0; k < kMlp; ++k) acc = fmaf(w.w2[j * kMlp + k], a1[k], acc);
+        a2[j] = mlp_act(acc, relu);
+    }
+}
+
+// H5 for one network and row on the host, from the head's gradient d_out[n_out]
+void host_heads_mlp_bwd(const HeadsNetW& w, const float* d_out, const float* a1, const float* a2, bool relu, float* d_z1,
+                        float* d_z2, float* d_h) {
+    for (int k = 0; k < kMlp; ++k) {
+        float s = 0.0f;
+        for (int j = 0; j < w.n_out; ++j) s = fmaf(d_out[j], w.w3[j * kMlp + k], s);
+        d_z2[k] = act_backward(s, a2[k], relu);
+    }
+    for (int k = 0; k < kMlp; ++k) {
+        float s = 0.0f;
+        for (int u = 0; u < kMlp; ++u) s = fmaf(d_z2[u], w.w2[u * kMlp + k], s);
+        d_z1[k] = act_backward(s, a1[k], relu);
+    }
+    for (int k = 0; k < kHid; ++k) {
+        float s = 0.0f;
+        for (int u = 0; u < kMlp; ++u) s = fmaf(d_z1[u], w.w1[u * kHid + k], s);
+        d_h[k] = s;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -2155,6 +2647,111 @@ ha_status ha_host_ppo_loss(int64_t n_rows, const ha_ppo_loss_io* io, const ha_pp
                            loss_sum_host(n_rows, [&](int64_t r) { return t[(size_t)r].kl; }),
                            loss_sum_host(n_rows, [&](int64_t r) { return t[(size_t)r].clipped; })};
     loss_stats(tot, k.normalize ? mean : 0.0, sd, k, io->stats);   // L5
+    return HE_OK;
+}
+
+size_t ha_ppo_heads_workspace_bytes(int64_t n_rows) {
+    if (check_heads_rows(n_rows) != HE_OK) return 0;
+    return kHpart * sizeof(float) + (size_t)((n_rows - 1) / HA_LOSS_BLOCK + 1) * kAct * sizeof(double);
+}
+
+ha_status ha_ppo_heads_forward(int64_t n_rows, const ha_ppo_heads_weights* weights, const ha_ppo_heads_fwd* io,
+                               void* workspace, void* stream) {
+    ha_status st = check_heads_fwd(n_rows, weights, io, 15u, 7u);
+    if (st != HE_OK) return st;
+    st = check_workspace(workspace);
+    if (st != HE_OK) return st;
+    st = heads_pack(weights, workspace, stream);
+    if (st != HE_OK) return st;
+    HeadsFwdParams p;
+    p.n = n_rows;
+    p.relu = weights->activation == HA_ACT_RELU;
+    p.io = *io;
+    p.net[0] = heads_net(weights, false);
+    p.net[1] = heads_net(weights, true);
+    p.ws = (const float*)workspace;
+    // enough workgroups to fill the device twice over, then up to a block's tiles each
+    const int64_t ntiles = (n_rows - 1) / kHRows + 1;
+    const int64_t per = ntiles / 512;
+    p.tiles_per_wg = (int32_t)(per < 1 ? 1 : (per > kHTiles ? kHTiles : per));
+    const dim3 grid((unsigned)((ntiles - 1) / p.tiles_per_wg + 1), 2);
+    return launch(nullptr, heads_fwd_kernel, grid, dim3(kThreads), stream, "heads_fwd_kernel", p);
+}
+
+ha_status ha_ppo_heads_backward(int64_t n_rows, const ha_ppo_heads_weights* weights, const ha_ppo_heads_bwd* io,
+                                void* workspace, void* stream) {
+    ha_status st = check_heads_bwd(n_rows, weights, io, 15u, 7u);
+    if (st != HE_OK) return st;
+    st = check_workspace(workspace);
+    if (st != HE_OK) return st;
+    st = heads_pack(weights, workspace, stream);
+    if (st != HE_OK) return st;
+    HeadsBwdParams p;
+    p.n = n_rows;
+    p.relu = weights->activation == HA_ACT_RELU;
+    p.nb = (int32_t)((n_rows - 1) / HA_LOSS_BLOCK + 1);
+    p.io = *io;
+    p.net[0] = heads_net(weights, false);
+    p.net[1] = heads_net(weights, true);
+    p.ws = (const float*)workspace;
+    p.part = (double*)((float*)workspace + kHpart);
+    st = launch(nullptr, heads_bwd_kernel, dim3((unsigned)p.nb, 2), dim3(kThreads), stream, "heads_bwd_kernel", p);
+    if (st != HE_OK) return st;
+    return launch(nullptr, heads_lsd_kernel, dim3(1), dim3(kLossLanes), stream, "heads_lsd_kernel", (const double*)p.part,
+                  (int)p.nb, io->d_log_std);
+}
+
+ha_status ha_host_ppo_heads_forward(int64_t n_rows, const ha_ppo_heads_weights* weights, const ha_ppo_heads_fwd* io) {
+    const ha_status st = check_heads_fwd(n_rows, weights, io, 3u, 3u);
+    if (st != HE_OK) return st;
+    const bool relu = weights->activation == HA_ACT_RELU;
+    const HeadsNetW pi = heads_net(weights, false), vf = heads_net(weights, true);
+    const float* ls = weights->log_std;
+    const float stdv[kAct] = {policy_std(ls[0]), policy_std(ls[1])};
+    const float ent = heads_entropy(ls);
+    for (int64_t r = 0; r < n_rows; ++r) {
+        float* a2 = io->a2_pi + r * kMlp;
+        host_heads_mlp(pi, io->h_pi + r * kHid, relu, io->a1_pi + r * kMlp, a2);
+        float mean[kAct];
+        for (int j = 0; j < kAct; ++j) {
+            float m = pi.b3[j];
+            for (int k = 0; k < kMlp; ++k) m = fmaf(pi.w3[j * kMlp + k], a2[k], m);
+            mean[j] = io->mean[r * kAct + j] = m;
+        }
+        io->log_prob[r] = heads_log_prob(io->actions + r * kAct, mean, ls, stdv);
+        io->entropy[r] = ent;
+        a2 = io->a2_vf + r * kMlp;
+        host_heads_mlp(vf, io->h_vf + r * kHid, relu, io->a1_vf + r * kMlp, a2);
+        float v = vf.b3[0];
+        for (int k = 0; k < kMlp; ++k) v = fmaf(vf.w3[k], a2[k], v);
+        io->values[r] = v;
+    }
+    return HE_OK;
+}
+
+ha_status ha_host_ppo_heads_backward(int64_t n_rows, const ha_ppo_heads_weights* weights, const ha_ppo_heads_bwd* io) {
+    const ha_status st = check_heads_bwd(n_rows, weights, io, 3u, 3u);
+    if (st != HE_OK) return st;
+    const bool relu = weights->activation == HA_ACT_RELU;
+    const HeadsNetW pi = heads_net(weights, false), vf = heads_net(weights, true);
+    const float* ls = weights->log_std;
+    const float stdv[kAct] = {policy_std(ls[0]), policy_std(ls[1])};
+    for (int64_t r = 0; r < n_rows; ++r) {   // H4, H5
+        float d_mean[kAct];
+        for (int j = 0; j < kAct; ++j) {
+            const double z = gauss_z(io->actions[r * kAct + j], io->mean[r * kAct + j], stdv[j]);
+            d_mean[j] = io->d_mean[r * kAct + j] = heads_d_mean(io->d_log_prob[r], z, stdv[j]);
+        }
+        host_heads_mlp_bwd(pi, d_mean, io->a1_pi + r * kMlp, io->a2_pi + r * kMlp, relu, io->d_z1_pi + r * kMlp,
+                           io->d_z2_pi + r * kMlp, io->d_h_pi + r * kHid);
+        host_heads_mlp_bwd(vf, io->d_values + r, io->a1_vf + r * kMlp, io->a2_vf + r * kMlp, relu, io->d_z1_vf + r * kMlp,
+                           io->d_z2_vf + r * kMlp, io->d_h_vf + r * kHid);
+    }
+    for (int j = 0; j < kAct; ++j)   // H6
+        io->d_log_std[j] = (float)loss_sum_host(n_rows, [&](int64_t r) {
+            const double z = gauss_z(io->actions[r * kAct + j], io->mean[r * kAct + j], stdv[j]);
+            return heads_lsd_term(io->d_log_prob[r], z, io->d_entropy[r]);
+        });
     return HE_OK;
 }
 

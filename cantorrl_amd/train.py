@@ -19,6 +19,10 @@ module.state_dict()) re-packs the policy on the device: an iteration without a h
 With ppo_update(loss="kernel") the loss, its statistics and its gradients with respect to values,
 log_prob and entropy are libhedgeactor's ha_ppo_loss (ppo_loss_kernel, contract L1-L6).
 
+With RecurrentPPOModule(heads="kernel") the part after the LSTMs (the two 64-64 MLPs, action_net, value_net,
+the log-probability and the entropy) is libhedgeactor's ha_ppo_heads_forward / _backward (ppo_heads, contract
+H1-H6): on a freshly collected buffer evaluate_actions then returns the buffer's own values and log_probs.
+
 By default only the LSTM is a kernel: nn.LSTM has no per-step reset, so sb3_contrib's
 _process_sequence runs one LSTM call per time step, forward and again in autograd's backward.  Here a workgroup walks all L
 steps of its 32 envs inside one launch, actor and critic side by side.  The MLPs, the heads, the
@@ -247,6 +251,168 @@ def lstm_sequence_pair(x, episode_starts, actor, critic, host=None, weight_grads
     return _LstmSeq.apply(host, _weight_grads_mode(weight_grads), x, episode_starts, *actor, *critic)
 
 
+# --------------------------------------------------------------------------- the heads as kernels
+HEADS = ("torch", "kernel")
+HEADS_TENSORS = ("w1", "b1", "w2", "b2", "w3", "b3", "log_std", "v1", "vb1", "v2", "vb2", "v3", "vb3")
+_HEADS_SHAPES = dict(w1=(MLP, HIDDEN), b1=(MLP,), w2=(MLP, MLP), b2=(MLP,), w3=(ACT_DIM, MLP), b3=(ACT_DIM,),
+                     log_std=(ACT_DIM,), v1=(MLP, HIDDEN), vb1=(MLP,), v2=(MLP, MLP), vb2=(MLP,), v3=(1, MLP), vb3=(1,))
+HEADS_FWD_IN = ("h_pi", "h_vf", "actions")
+HEADS_FWD_OUT = ("values", "log_prob", "entropy", "mean", "a1_pi", "a2_pi", "a1_vf", "a2_vf")
+HEADS_BWD_IN = ("d_values", "d_log_prob", "d_entropy", "actions", "mean", "a1_pi", "a2_pi", "a1_vf", "a2_vf")
+HEADS_BWD_OUT = ("d_h_pi", "d_h_vf", "d_z1_pi", "d_z2_pi", "d_z1_vf", "d_z2_vf", "d_mean", "d_log_std")
+
+
+class HaPpoHeadsWeights(ctypes.Structure):
+    _fields_ = [(k, _VP) for k in HEADS_TENSORS] + [("activation", ctypes.c_int32)]
+
+
+class HaPpoHeadsFwd(ctypes.Structure):
+    _fields_ = [(k, _VP) for k in HEADS_FWD_IN + HEADS_FWD_OUT]
+
+
+class HaPpoHeadsBwd(ctypes.Structure):
+    _fields_ = [(k, _VP) for k in HEADS_BWD_IN + HEADS_BWD_OUT]
+
+
+def _heads_mode(mode):
+    if mode not in HEADS:
+        raise ValueError(f"heads must be one of {HEADS}, not {mode!r}")
+    return mode
+
+
+def _heads_row_shapes(R):
+    one, two, mid, wide = (R,), (R, ACT_DIM), (R, MLP), (R, HIDDEN)
+    return dict(h_pi=wide, h_vf=wide, actions=two, values=one, log_prob=one, entropy=one, mean=two, a1_pi=mid,
+                a2_pi=mid, a1_vf=mid, a2_vf=mid, d_values=one, d_log_prob=one, d_entropy=one, d_h_pi=wide, d_h_vf=wide,
+                d_z1_pi=mid, d_z2_pi=mid, d_z1_vf=mid, d_z2_vf=mid, d_mean=two, d_log_std=(ACT_DIM,))
+
+
+def _heads_call(op, struct, rows, inputs, outputs, weights, activation, host):
+    """What ppo_heads_forward / _backward share: ha_<op> on a HIP device or ha_host_<op> over `rows`, a dict
+    of the `inputs` tensors with R rows each, and `weights`, the 13 HEADS_TENSORS -> a dict of the new
+    `outputs` tensors."""
+    lib = load()
+    if activation not in ("tanh", "relu"):
+        raise ValueError(f"activation must be 'tanh' or 'relu', not {activation!r}")
+    first = rows[inputs[0]]
+    dev, R = first.device, int(first.shape[0]) if first.dim() else 0
+    host = dev.type == "cpu" if host is None else bool(host)
+    if host != (dev.type == "cpu"):
+        raise ValueError("host=True takes CPU tensors, host=False tensors on a HIP device")
+    if len(weights) != len(HEADS_TENSORS):
+        raise ValueError(f"weights: the {len(HEADS_TENSORS)} tensors {HEADS_TENSORS}")
+    shapes = _heads_row_shapes(R)
+    w, io, keep = HaPpoHeadsWeights(), struct(), []
+    for name, t in zip(HEADS_TENSORS, weights):
+        t = _f32(t, _HEADS_SHAPES[name], name, dev)
+        keep.append(t)
+        setattr(w, name, t.data_ptr())
+    w.activation = 1 if activation == "relu" else 0
+    for name in inputs:
+        t = _f32(rows[name], shapes[name], name, dev)
+        keep.append(t)
+        setattr(io, name, t.data_ptr())
+    out = {name: torch.empty(shapes[name], dtype=torch.float32, device=dev) for name in outputs}
+    for name, t in out.items():
+        setattr(io, name, t.data_ptr())
+    if host:
+        st = getattr(lib, "ha_host_" + op)(R, ctypes.byref(w), ctypes.byref(io))
+    else:
+        with torch.cuda.device(dev):
+            ws = torch.empty(lib.ha_ppo_heads_workspace_bytes(R) or 16, dtype=torch.uint8, device=dev)
+            st = getattr(lib, "ha_" + op)(R, ctypes.byref(w), ctypes.byref(io), ws.data_ptr(), _stream(dev))
+    _check(lib, st, "ha_" + op)
+    return out
+
+
+def ppo_heads_forward(h_pi, h_vf, actions, weights, activation="tanh", host=None):
+    """ha_ppo_heads_forward (contract H1-H3; CPU tensors run ha_host_ppo_heads_forward, the same bits):
+    h_pi, h_vf [R,128], actions [R,2], weights = the 13 HEADS_TENSORS in torch layout -> a dict of values,
+    log_prob, entropy [R], mean [R,2] and a1_pi, a2_pi, a1_vf, a2_vf [R,64] (saved for the backward).
+    No autograd.  A refusal of the library is a ValueError with its message."""
+    return _heads_call("ppo_heads_forward", HaPpoHeadsFwd, dict(h_pi=h_pi, h_vf=h_vf, actions=actions), HEADS_FWD_IN,
+                       HEADS_FWD_OUT, weights, activation, host)
+
+
+def ppo_heads_backward(d_values, d_log_prob, d_entropy, actions, saved, weights, activation="tanh", host=None):
+    """ha_ppo_heads_backward (contract H4-H6): the three gradients [R], actions [R,2] and `saved`, the
+    forward's dict (mean, a1_pi, a2_pi, a1_vf, a2_vf) -> a dict of d_h_pi, d_h_vf [R,128], d_z1_pi, d_z2_pi,
+    d_z1_vf, d_z2_vf [R,64], d_mean [R,2], d_log_std [2].  No autograd."""
+    rows = dict(saved, d_values=d_values, d_log_prob=d_log_prob, d_entropy=d_entropy, actions=actions)
+    return _heads_call("ppo_heads_backward", HaPpoHeadsBwd, rows, HEADS_BWD_IN, HEADS_BWD_OUT, weights, activation, host)
+
+
+def _blocked_tn(d, x, block=128):
+    """d^T x and d's column sums over the rows of d [R,m], x [R,k] as f64 tensors: one batched f32 GEMM sums
+    blocks of `block` rows, the blocks' results are added in f64 (as weight_grads)."""
+    R, f64 = d.shape[0], torch.float64
+    nb = R // block
+    w = torch.zeros((d.shape[1], x.shape[1]), dtype=f64, device=d.device)
+    b = torch.zeros(d.shape[1], dtype=f64, device=d.device)
+    if nb:
+        d3 = d[:nb * block].view(nb, block, -1)
+        w += torch.bmm(d3.transpose(1, 2), x[:nb * block].view(nb, block, -1)).sum(0, dtype=f64)
+        b += d3.sum(1).sum(0, dtype=f64)
+    if R > nb * block:
+        w += (d[nb * block:].t() @ x[nb * block:]).to(f64)
+        b += d[nb * block:].sum(0).to(f64)
+    return w, b
+
+
+def heads_weight_grads(d_z, inp):
+    """The 13 gradients of HEADS_TENSORS, f32, from the per-row tensors: d_z = ppo_heads_backward's dict plus
+    d_values [R]; inp = dict(h_pi, h_vf, a1_pi, a2_pi, a1_vf, a2_vf).  dW = d^T input and db = sum d per layer
+    through _blocked_tn (blocks of 128 rows in one batched f32 GEMM, the blocks added in f64); log_std's is
+    contract H6's d_log_std."""
+    f32 = torch.float32
+    g = {}
+    for net, (w1, b1, w2, b2, w3, b3), d_out in (("pi", HEADS_TENSORS[:6], d_z["d_mean"]),
+                                                 ("vf", HEADS_TENSORS[7:], d_z["d_values"].reshape(-1, 1))):
+        for wn, bn, d, x in ((w1, b1, d_z["d_z1_" + net], inp["h_" + net]), (w2, b2, d_z["d_z2_" + net], inp["a1_" + net]),
+                             (w3, b3, d_out, inp["a2_" + net])):
+            w, b = _blocked_tn(d, x)
+            g[wn], g[bn] = w.to(f32), b.to(f32)
+    g["log_std"] = d_z["d_log_std"]
+    return tuple(g[k] for k in HEADS_TENSORS)
+
+
+class _PpoHeads(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, host, activation, h_pi, h_vf, actions, *weights):
+        lead = h_pi.shape[:-1]
+        flat = (h_pi.reshape(-1, HIDDEN), h_vf.reshape(-1, HIDDEN), actions.reshape(-1, ACT_DIM))
+        out = ppo_heads_forward(*flat, weights, activation, host=host)
+        ctx.save_for_backward(*flat, *weights, *(out[k] for k in HEADS_BWD_IN[4:]))
+        ctx.host, ctx.activation, ctx.lead = host, activation, lead
+        return tuple(out[k].view(lead) for k in ("values", "log_prob", "entropy"))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_values, d_log_prob, d_entropy):
+        h_pi, h_vf, actions = ctx.saved_tensors[:3]
+        weights = ctx.saved_tensors[3:3 + len(HEADS_TENSORS)]
+        saved = dict(zip(HEADS_BWD_IN[4:], ctx.saved_tensors[3 + len(HEADS_TENSORS):]))
+        R = h_pi.shape[0]
+        d = [torch.zeros(R, dtype=torch.float32, device=h_pi.device) if g is None else g.reshape(R)
+             for g in (d_values, d_log_prob, d_entropy)]
+        out = ppo_heads_backward(*d, actions, saved, weights, ctx.activation, host=ctx.host)
+        grads = heads_weight_grads(dict(out, d_values=d[0]), dict(saved, h_pi=h_pi, h_vf=h_vf))
+        return (None, None, out["d_h_pi"].view(*ctx.lead, HIDDEN), out["d_h_vf"].view(*ctx.lead, HIDDEN), None, *grads)
+
+
+def ppo_heads(h_pi, h_vf, actions, w1, b1, w2, b2, w3, b3, log_std, v1, vb1, v2, vb2, v3, vb3, activation="tanh",
+              host=None):
+    """The part of evaluate_actions after the LSTMs as libhedgeactor's kernels (contract H1-H6 of
+    include/hedge_actor.h): h_pi, h_vf [..., 128], actions [..., 2] and the 13 HEADS_TENSORS -> (values,
+    log_prob, entropy) [...], differentiable in h_pi, h_vf and the 13 tensors; actions get no gradient.
+    Forward: heads_pack_kernel + heads_fwd_kernel; backward: heads_pack_kernel + heads_bwd_kernel +
+    heads_lsd_kernel, then the weight gradients from the per-row gradients with heads_weight_grads (torch).
+    host=True (default for CPU tensors) runs the host build: the same bits."""
+    host = h_pi.device.type == "cpu" if host is None else bool(host)
+    return _PpoHeads.apply(host, activation, h_pi, h_vf, actions, w1, b1, w2, b2, w3, b3, log_std, v1, vb1, v2, vb2, v3,
+                           vb3)
+
+
 # --------------------------------------------------------------------------- the policy as a torch module
 class _Lstm(torch.nn.Module):
     """The four tensors of a one-layer nn.LSTM under nn.LSTM's names (a container: the op is lstm_sequence)."""
@@ -277,12 +443,14 @@ class RecurrentPPOModule(torch.nn.Module):
     state_dict() feeds RecurrentPolicy.load_state_dict as it is.  activation: "tanh" (SB3's default)
     or "relu".  obs_mean / obs_var: the statistics a RecurrentPolicy applies to raw obs (contract step
     2); leave them out when the buffer holds normalised obs (a DeviceVecNormalize env).  weight_grads:
-    lstm_sequence's keyword, passed on by evaluate_actions."""
+    lstm_sequence's keyword, passed on by evaluate_actions.  heads: "torch" runs the part after the LSTMs
+    (self.heads) in torch, "kernel" as ppo_heads (ha_ppo_heads_forward / _backward, contract H1-H6)."""
 
     def __init__(self, activation="tanh", obs_mean=None, obs_var=None, clip_obs=10.0, epsilon=1e-8,
-                 weight_grads="torch"):
+                 weight_grads="torch", heads="torch"):
         super().__init__()
         self.weight_grads = _weight_grads_mode(weight_grads)
+        self.heads_mode = _heads_mode(heads)
         acts = {"tanh": torch.nn.Tanh, "relu": torch.nn.ReLU}
         if activation not in acts:
             raise ValueError(f"activation must be one of {sorted(acts)}, not {activation!r}")
@@ -318,11 +486,11 @@ class RecurrentPPOModule(torch.nn.Module):
         return cls.from_state_dict(_read_sb3_zip(path), normalization=normalization, **kw)
 
     @classmethod
-    def from_policy(cls, policy, device=None, weight_grads="torch"):
+    def from_policy(cls, policy, device=None, weight_grads="torch", heads="torch"):
         """The tensors, activation and statistics of an agent.RecurrentPolicy, on its device."""
         _, a = policy._host_weights()   # after a load_device_state_dict: the tensors it read
         m = cls(activation=policy.activation, obs_mean=a.get("obs_mean"), obs_var=a.get("obs_var"),
-                clip_obs=policy.clip_obs, epsilon=policy.epsilon, weight_grads=weight_grads)
+                clip_obs=policy.clip_obs, epsilon=policy.epsilon, weight_grads=weight_grads, heads=heads)
         m.load_state_dict({k: torch.from_numpy(a[f].copy()) for k, f, _ in POLICY_KEYS})
         return m.to(policy.device_name if device is None else device)
 
@@ -343,6 +511,13 @@ class RecurrentPPOModule(torch.nn.Module):
         dist = torch.distributions.Normal(mean, torch.ones_like(mean) * self.log_std.exp())
         return values, dist.log_prob(actions).sum(-1), dist.entropy().sum(-1)
 
+    def heads_tensors(self):
+        """The 13 tensors after the LSTMs in HEADS_TENSORS' order."""
+        pi, vf = self.mlp_extractor.policy_net, self.mlp_extractor.value_net
+        return (pi[0].weight, pi[0].bias, pi[2].weight, pi[2].bias, self.action_net.weight, self.action_net.bias,
+                self.log_std, vf[0].weight, vf[0].bias, vf[2].weight, vf[2].bias, self.value_net.weight,
+                self.value_net.bias)
+
     def evaluate_actions(self, obs, actions, episode_starts, states0, host=None):
         """sb3_contrib's evaluate_actions over whole sequences: obs [L,B,13], actions [L,B,2],
         episode_starts [L,B], states0 = (h_pi, c_pi, h_vf, c_vf) [B,128] before step 0 ->
@@ -351,6 +526,8 @@ class RecurrentPPOModule(torch.nn.Module):
         h_pi, h_vf = lstm_sequence_pair(x, episode_starts, (states0[0], states0[1], *self.lstm_actor.tensors()),
                                         (states0[2], states0[3], *self.lstm_critic.tensors()), host=host,
                                         weight_grads=self.weight_grads)
+        if self.heads_mode == "kernel":
+            return ppo_heads(h_pi, h_vf, actions, *self.heads_tensors(), activation=self.activation, host=host)
         return self.heads(h_pi, h_vf, actions)
 
 
@@ -580,7 +757,8 @@ def ppo_update(module, optimizer, buffer, *, n_epochs=10, envs_per_batch=None, w
     clip_range 0.3, ent_coef 1e-5, vf_coef 0.5, max_grad_norm 0.5, n_epochs 10).  An optimizer with a
     clip_and_step method (DeviceAdam) clips and steps through it, any other through clip_grad_norm_ and
     step().  loss: "torch" is ppo_loss under autograd; "kernel" is ppo_loss_kernel (ha_ppo_loss, contract
-    L1-L6) on the heads' detached outputs, its three gradients handed to autograd where the heads stand.
+    L1-L6) on the heads' detached outputs, its three gradients handed to autograd where the heads stand (on
+    a module with heads="kernel" they enter ppo_heads' backward, ha_ppo_heads_backward, as they are).
     clip_range_vf (None: no value clip) is SB3's, against buffer.values.  target_kl is not built.
     Nothing synchronises
     with the host; returns the last minibatch's statistics and the mean loss as device scalars."""

@@ -5,8 +5,9 @@
  * per-episode sums of a closed-loop evaluation around he_step, and the training side: actor,
  * critic, action sampling and log-probability of a rollout step in one launch, GAE, and for the
  * PPO update both LSTMs over a stored sequence with per-step resets, forward and backward, their
- * weight gradients, the PPO loss with its gradients, the gradient-norm clip with Adam's step, and the
- * re-packing of a policy's handle from the updated device tensors.
+ * weight gradients, the MLP heads after them with the log-probability and the entropy, forward and
+ * backward, the PPO loss with its gradients, the gradient-norm clip with Adam's step, and the re-packing
+ * of a policy's handle from the updated device tensors.
  *
  * Conventions (as hedge_env.h): plain C types, every entry point returns an ha_status (the
  * he_status values), the last failure's message is ha_last_error(handle), no C++ exception
@@ -155,6 +156,29 @@
  *   L6. d_log_prob_i = active ? -(A' r) / N : +0; d_values_i = pass ? -((2 vf_coef) e) / N : +0;
  *       d_entropy_i = -ent_coef / N; each rounded once to f32.
  *   Nothing in L1-L6 depends on the grid.
+ *
+ * The PPO heads (ha_ppo_heads_forward / _backward: what evaluate_actions computes after the LSTMs, the two
+ * 64-64 MLPs, action_net, value_net, the Gaussian log-probability of the stored action and the entropy,
+ * and autograd's backward of it down to the LSTMs' outputs; restated).  Rows r = 0 .. R - 1, h_pi[r] and
+ * h_vf[r] of 128 each; every row is independent of the others except in H6.  f32, one rounding per
+ * operation, no contraction, unless it says f64.
+ *   H1. per network a1 = act(chain(b1; W1 h)), a2 = act(chain(b2; W2 a1)): step 5 with mlp_act.  Actor:
+ *       mean[j] = chain(b3[j]; w3[j] a2).  Critic: value = chain(vb3; v3 a2).  A chain is the k-ordered
+ *       fmaf chain from the bias: for the same tensors and the same h the bits of ha_policy_step's
+ *       mean_out and values.
+ *   H2. std[j] = f32(exp_f64(f64(log_std[j]))) (P3); log_prob is P6 with a = the row's stored action.
+ *   H3. entropy = f32(sum_j ((0.5 + 0.9189385332046727) + f64(log_std[j]))), f64, j in order from 0.
+ *   H4. z_j as in P6; d_mean[j] = f32(f64(d_log_prob) (z_j / f64(std[j]))), f64.  The critic's head
+ *       gradient is d_values.
+ *   H5. per network, d_out the head's gradient (d_mean[2], or d_values):
+ *         d_a2[k] = the fmaf chain from +0 over the head's rows j in order of d_out[j] w3[j][k]
+ *         d_z2[k] = d_a2[k] (1 - a2[k] a2[k]) for tanh; a2[k] > 0 ? d_a2[k] : +0 for relu
+ *         d_a1[k] = the fmaf chain from +0 over u = 0 .. 63 of d_z2[u] W2[u][k]; d_z1 from d_a1, a1 likewise
+ *         d_h[k], k = 0 .. 127 = the fmaf chain from +0 over u = 0 .. 63 of d_z1[u] W1[u][k]
+ *       v_mfma_f32_32x32x2_f32 with u as its k computes exactly these chains (as B4).
+ *   H6. d_log_std[j] = f32(sum_r (f64(d_log_prob_r) (z_rj z_rj - 1) + f64(d_entropy_r))), f64, the sum
+ *       of L1 over the rows (blocks of HA_LOSS_BLOCK, the same lane ownership and tree), R <= 2^22.
+ *   Nothing in H1-H6 depends on the grid.
  */
 #ifndef HEDGE_ACTOR_H
 #define HEDGE_ACTOR_H
@@ -526,6 +550,88 @@ ha_status ha_ppo_loss(int64_t n_rows, const ha_ppo_loss_io* io, const ha_ppo_los
 
 /* The same arithmetic on the host (L1-L6 taken literally), HOST pointers, no workspace. */
 ha_status ha_host_ppo_loss(int64_t n_rows, const ha_ppo_loss_io* io, const ha_ppo_loss_hyper* hyper);
+
+/* ---- the PPO heads: MLPs, action / value heads, log-probability, entropy, and their backward (H1-H6) ---- */
+
+/* The 13 tensors after the LSTMs, DEVICE pointers (HOST pointers for ha_host_ppo_heads_*), f32, torch
+ * layout, read as they stand when the call runs on the stream.  w1, w2, w3, b1, b2 and their critic
+ * counterparts 16-byte aligned, b3, vb3 and log_std 4-byte. */
+typedef struct ha_ppo_heads_weights {
+    const float* w1;       /* mlp_extractor.policy_net.0.weight [64][128] */
+    const float* b1;       /* mlp_extractor.policy_net.0.bias   [64]      */
+    const float* w2;       /* mlp_extractor.policy_net.2.weight [64][64]  */
+    const float* b2;       /* mlp_extractor.policy_net.2.bias   [64]      */
+    const float* w3;       /* action_net.weight [2][64] */
+    const float* b3;       /* action_net.bias   [2]     */
+    const float* log_std;  /* [2] */
+    const float* v1;       /* mlp_extractor.value_net.0.weight [64][128] */
+    const float* vb1;      /* mlp_extractor.value_net.0.bias   [64]      */
+    const float* v2;       /* mlp_extractor.value_net.2.weight [64][64]  */
+    const float* vb2;      /* mlp_extractor.value_net.2.bias   [64]      */
+    const float* v3;       /* value_net.weight [1][64] */
+    const float* vb3;      /* value_net.bias   [1]     */
+    int32_t activation;    /* ha_activation, both MLPs */
+} ha_ppo_heads_weights;
+
+/* The forward's rows.  [R][128], [R][64]: 16-byte aligned; [R][2]: 8-byte; [R]: 4-byte. */
+typedef struct ha_ppo_heads_fwd {
+    const float* h_pi;     /* [R][128] the actor LSTM's output */
+    const float* h_vf;     /* [R][128] the critic LSTM's */
+    const float* actions;  /* [R][2] the stored (unclipped) actions */
+    float* values;         /* [R] out */
+    float* log_prob;       /* [R] out */
+    float* entropy;        /* [R] out */
+    float* mean;           /* [R][2] out, saved for the backward */
+    float* a1_pi;          /* [R][64] out, saved for the backward: the actor's first hidden layer */
+    float* a2_pi;          /* [R][64] its second */
+    float* a1_vf;          /* [R][64] the critic's */
+    float* a2_vf;
+} ha_ppo_heads_fwd;
+
+/* The backward's rows, alignment as ha_ppo_heads_fwd; d_log_std 4-byte. */
+typedef struct ha_ppo_heads_bwd {
+    const float* d_values;   /* [R] ha_ppo_loss's three gradients */
+    const float* d_log_prob;
+    const float* d_entropy;
+    const float* actions;    /* [R][2] */
+    const float* mean;       /* [R][2] the forward's */
+    const float* a1_pi;      /* [R][64] the forward's */
+    const float* a2_pi;
+    const float* a1_vf;
+    const float* a2_vf;
+    float* d_h_pi;           /* [R][128] out */
+    float* d_h_vf;
+    float* d_z1_pi;          /* [R][64] out: the gradients of the pre-activations (the weight gradients' input) */
+    float* d_z2_pi;
+    float* d_z1_vf;
+    float* d_z2_vf;
+    float* d_mean;           /* [R][2] out */
+    float* d_log_std;        /* [2] out */
+} ha_ppo_heads_bwd;
+
+/* Bytes of the workspace both calls take: both networks' weights in the kernels' fragment order (W1, W2
+ * and their transposes), log_std with std, and two f64 per block of HA_LOSS_BLOCK rows (H6's s_b).  0 for
+ * an n_rows the calls refuse.  Each call packs what it reads (heads_pack_kernel in front), so the
+ * workspace carries nothing from call to call. */
+size_t ha_ppo_heads_workspace_bytes(int64_t n_rows);
+
+/* H1-H3 over n_rows rows: heads_pack_kernel, then heads_fwd_kernel over a grid of (groups of 64-row
+ * tiles, 2), y = actor / critic, a workgroup keeping its slice of the weights in registers over its tiles.
+ * H4-H6: heads_pack_kernel, heads_bwd_kernel over a grid of (blocks of HA_LOSS_BLOCK rows, 2), each actor
+ * workgroup writing its block's two sums of H6, then heads_lsd_kernel (one workgroup) adding them in block
+ * order.  No atomics, no waiting between workgroups: kernel boundaries are the only grid-wide ordering.
+ * Stream-ordered: no host synchronisation, no copy call, no allocation; capturable; the workspace (16-byte
+ * aligned) is the caller's.  Before any launch: n_rows outside [1, HA_LOSS_BLOCK HA_LOSS_MAX_BLOCKS] is
+ * HE_ESHAPE; a NULL or misaligned pointer or an unknown activation HE_EINVAL.  The message is
+ * ha_policy_last_error(NULL).  A refused call writes nothing. */
+ha_status ha_ppo_heads_forward(int64_t n_rows, const ha_ppo_heads_weights* weights, const ha_ppo_heads_fwd* io,
+                               void* workspace, void* stream);
+ha_status ha_ppo_heads_backward(int64_t n_rows, const ha_ppo_heads_weights* weights, const ha_ppo_heads_bwd* io,
+                                void* workspace, void* stream);
+
+/* The same arithmetic on the host (H1-H6 taken literally), HOST pointers (4-byte aligned), no workspace. */
+ha_status ha_host_ppo_heads_forward(int64_t n_rows, const ha_ppo_heads_weights* weights, const ha_ppo_heads_fwd* io);
+ha_status ha_host_ppo_heads_backward(int64_t n_rows, const ha_ppo_heads_weights* weights, const ha_ppo_heads_bwd* io);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,7 @@ autograd, f32.  And one ppo_update epoch over a buffer of the first shape.  HIP 
 call, warm-up first, the median.
 
     python tools/train_time.py [--reps R] [--out FILE.jsonl] [--shapes L,B ...] [--weight-grads torch|kernel|both]
-                               [--optimizer] [--loss]
+                               [--optimizer] [--loss] [--heads]
 
 --weight-grads torch (the default) times lstm_sequence_pair as it is called by default, its weight
 gradients from train.weight_grads.  kernel times forward plus backward with weight_grads="kernel", and
@@ -32,6 +32,13 @@ and entropy against train.ppo_loss_kernel (ha_ppo_loss) on the same tensors at 6
 beside the bytes floor (40 B a row at the 6.29 TB/s copy ceiling), and one ppo_update epoch with
 loss="torch" and loss="kernel" (DeviceAdam) at 32 x 2 (envs_per_batch 1) and 256 x 4,096 (envs_per_batch
 1,024).  Both paths run in this process.
+
+--heads times, instead, the part of evaluate_actions after the LSTMs, forward plus backward to h_pi, h_vf and
+the 13 tensors: RecurrentPPOModule.heads under autograd against train.ppo_heads (ha_ppo_heads_forward /
+_backward, then the weight gradients' torch GEMMs) on the same tensors at 64, 262,144 and 1,048,576 rows, the
+six kernel launches alone beside their bytes floor (5,160 B a row at the 6.29 TB/s copy ceiling), and one
+ppo_update epoch (DeviceAdam, loss="kernel", weight_grads="kernel") with heads="torch" and heads="kernel" at
+32 x 2 (envs_per_batch 1) and 256 x 4,096 (envs_per_batch 1,024).  Both paths run in this process.
 """
 import argparse
 import copy
@@ -287,6 +294,62 @@ def measure_loss(reps):
     return lines
 
 
+HEADS_ROWS = (64, 262144, 1 << 20)
+# per row, each once.  Forward: h_pi, h_vf (1,024) and actions (8) read; a1, a2 of both networks (1,024), mean (8),
+# values, log_prob, entropy (12) written.  Backward: a1, a2 (1,024), the three gradients (12), actions, mean (16)
+# read; d_h (1,024), d_z1, d_z2 (1,024), d_mean (8) written.
+BYTES_HEADS = (1024 + 8 + 1024 + 8 + 12) + (1024 + 12 + 16 + 1024 + 1024 + 8)
+
+
+def measure_heads(reps):
+    """--heads: the heads alone per row count (forward plus backward to h and the 13 tensors), then one
+    ppo_update epoch per shape with either heads path."""
+    lines = []
+    g = torch.Generator(device=DEV).manual_seed(6)
+    m = module(np.random.default_rng(0))
+    for rows in HEADS_ROWS:
+        h = [(torch.rand((rows, 128), device=DEV, generator=g) * 2 - 1).requires_grad_() for _ in range(2)]
+        actions = torch.randn((rows, 2), device=DEV, generator=g)
+        d = [torch.randn(rows, device=DEV, generator=g) / rows for _ in range(3)]
+        w = list(m.heads_tensors())
+
+        def torch_path():
+            torch.autograd.grad(m.heads(h[0], h[1], actions), h + w, d)
+
+        def kernel_path():
+            torch.autograd.grad(train.ppo_heads(h[0], h[1], actions, *w), h + w, d)
+
+        def kernels_alone():
+            f = train.ppo_heads_forward(h[0], h[1], actions, w)
+            train.ppo_heads_backward(*d, actions, {k: f[k] for k in train.HEADS_BWD_IN[4:]}, w)
+
+        r = dict(mode="heads", rows=rows, reps=reps, device=torch.cuda.get_device_name(0))
+        r["heads_torch_us"] = round(median_us(torch_path, reps, 3), 1)
+        r["heads_kernel_us"] = round(median_us(kernel_path, reps, 3), 1)
+        r["heads_kernels_alone_us"] = round(median_us(kernels_alone, reps, 3), 1)
+        r["heads_speedup"] = round(r["heads_torch_us"] / r["heads_kernel_us"], 2)
+        r["heads_floor_bytes_us"] = round(rows * BYTES_HEADS / COPY_CEILING * 1e6, 2)
+        r["heads_kernels_frac_of_bytes_floor"] = round(r["heads_floor_bytes_us"] / r["heads_kernels_alone_us"], 3)
+        lines.append(r)
+        del h, actions, d
+        torch.cuda.empty_cache()
+    for K, n, per in LOSS_UPDATES:
+        u = dict(mode="heads_update", optimizer="device_adam", loss="kernel", weight_grads="kernel",
+                 device=torch.cuda.get_device_name(0))
+        for heads in train.HEADS:
+            mm = copy.deepcopy(m)
+            mm.heads_mode, mm.weight_grads = heads, "kernel"
+            res = measure_update_with(mm, train.DeviceAdam(mm.parameters(), lr=1e-5, eps=1e-5), K, n, per, reps,
+                                      loss="kernel")
+            u[f"ppo_update_epoch_heads_{heads}_us"] = res.pop("ppo_update_epoch_us")
+            u.update(res)
+            del mm
+            torch.cuda.empty_cache()
+        u["heads_kernel_speedup"] = round(u["ppo_update_epoch_heads_torch_us"] / u["ppo_update_epoch_heads_kernel_us"], 3)
+        lines.append(u)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="*", default=["256,4096", "256,16384", "32,2"])
@@ -297,15 +360,20 @@ def main():
                     help="time the clip + optimizer step and the policy refresh against their baselines instead")
     ap.add_argument("--loss", action="store_true",
                     help="time ppo_loss_kernel against ppo_loss, alone and inside ppo_update, instead")
+    ap.add_argument("--heads", action="store_true",
+                    help="time ppo_heads against RecurrentPPOModule.heads, alone and inside ppo_update, instead")
     a = ap.parse_args()
     lines = []
-    if a.loss:
+    if a.heads:
+        lines = [json.dumps(r) for r in measure_heads(a.reps)]
+        print("\n".join(lines), flush=True)
+    elif a.loss:
         lines = [json.dumps(r) for r in measure_loss(a.reps)]
         print("\n".join(lines), flush=True)
     elif a.optimizer:
         lines = [json.dumps(r) for r in measure_optimizer([tuple(int(v) for v in s.split(",")) for s in a.shapes], a.reps)]
         print("\n".join(lines), flush=True)
-    for k, s in enumerate([] if a.optimizer or a.loss else a.shapes):
+    for k, s in enumerate([] if a.optimizer or a.loss or a.heads else a.shapes):
         L, B = (int(v) for v in s.split(","))
         r, m = measure(L, B, a.reps, a.weight_grads)
         if k == 0 and a.weight_grads != "kernel":
