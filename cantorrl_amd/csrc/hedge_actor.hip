@@ -381,11 +381,19 @@ ha_status create_handle(const std::vector<float>& hbuf, H** out) {
     return st;
 }
 
-// one network's HOST tensors, torch layout; w3 is [n_out][64]
+// the part of a network after its LSTM, torch layout; w3 is [n_out][64].  A member of HeadsFwdParams and
+// HeadsBwdParams: its layout is a kernel argument.
+struct HeadsNetW {
+    const float *w1, *b1, *w2, *b2, *w3, *b3;
+    int n_out;
+};
+
+// one network's HOST tensors, torch layout
 struct HostNet {
     const float *w_ih, *w_hh, *b_ih, *b_hh, *w1, *b1, *w2, *b2, *w3, *b3;
     int n_out;
     bool complete() const { return w_ih && w_hh && b_ih && b_hh && w1 && b1 && w2 && b2 && w3 && b3; }
+    HeadsNetW heads() const { return {w1, b1, w2, b2, w3, b3, n_out}; }
 };
 
 template <class W>   // ha_weights or ha_policy_weights
@@ -529,6 +537,27 @@ struct HostNorm {
     }
 };
 
+// THE 64-64 MLP of the contract on the host (step 5, H1) for one env or row: the two layers into a1, a2
+void host_mlp(const HeadsNetW& w, const float* h, bool relu, float* a1, float* a2) {
+    for (int j = 0; j < kMlp; ++j) {
+        float acc = w.b1[j];
+        for (int k = 0; k < kHid; ++k) acc = fmaf(w.w1[j * kHid + k], h[k], acc);
+        a1[j] = mlp_act(acc, relu);
+    }
+    for (int j = 0; j < kMlp; ++j) {
+        float acc = w.b2[j];
+        for (int k = 0; k < kMlp; ++k) acc = fmaf(w.w2[j * kMlp + k], a1[k], acc);
+        a2[j] = mlp_act(acc, relu);
+    }
+}
+
+// output j of the head: chain(b3; w3 a2)
+inline float host_head(const HeadsNetW& w, int j, const float* a2) {
+    float m = w.b3[j];
+    for (int k = 0; k < kMlp; ++k) m = fmaf(w.w3[j * kMlp + k], a2[k], m);
+    return m;
+}
+
 // Contract steps 1, 3-5 for one env on the host: x is the (normalised) obs; h, c are read unless
 // fresh and written when write_state; a2 receives the last hidden layer.
 void host_net_env(const HostNet& w, const float* x, bool fresh, float* h, float* c, bool write_state, bool relu,
@@ -545,22 +574,7 @@ void host_net_env(const HostNet& w, const float* x, bool fresh, float* h, float*
         memcpy(h, hn, sizeof hn);
         memcpy(c, cn, sizeof cn);
     }
-    for (int j = 0; j < kMlp; ++j) {
-        float acc = w.b1[j];
-        for (int k = 0; k < kHid; ++k) acc = fmaf(w.w1[j * kHid + k], hn[k], acc);
-        a1[j] = mlp_act(acc, relu);
-    }
-    for (int j = 0; j < kMlp; ++j) {
-        float acc = w.b2[j];
-        for (int k = 0; k < kMlp; ++k) acc = fmaf(w.w2[j * kMlp + k], a1[k], acc);
-        a2[j] = mlp_act(acc, relu);
-    }
-}
-
-inline float host_head(const HostNet& w, int j, const float* a2) {
-    float m = w.b3[j];
-    for (int k = 0; k < kMlp; ++k) m = fmaf(w.w3[j * kMlp + k], a2[k], m);
-    return m;
+    host_mlp(w.heads(), hn, relu, a1, a2);
 }
 
 // the blob of a policy: [actor | critic | log_std, std | statistics]
@@ -874,8 +888,12 @@ ha_status check_seq(int64_t n_nets, int64_t L, int64_t B) {
 
 inline bool bad_ptr(const void* q, uintptr_t mask) { return !q || (((uintptr_t)q) & mask); }
 
-ha_status check_workspace(const void* workspace) {
-    return bad_ptr(workspace, 15u) ? fail_to(nullptr, HE_EINVAL, "workspace must be non-NULL and 16-byte aligned") : HE_OK;
+// align: 16, or 8 where the workspace holds f64 sums alone
+ha_status check_workspace(const void* workspace, unsigned align = 16) {
+    if (!bad_ptr(workspace, align - 1)) return HE_OK;
+    char m[64];
+    snprintf(m, sizeof m, "workspace must be non-NULL and %u-byte aligned", align);
+    return fail_to(nullptr, HE_EINVAL, m);
 }
 
 ha_status check_seq_fwd(int64_t n_nets, int64_t L, int64_t B, const void* x, const void* starts,
@@ -1254,6 +1272,28 @@ __global__ __launch_bounds__(256) void policy_pack_kernel(const PolicyPackParams
 // workspace.  opt_adam_kernel: the same grid; every thread adds the s_b in order (the same loads and
 // adds in every lane of every workgroup: the same bits), then updates its element.  The tensors and
 // the first block of each travel in the kernel's arguments.
+constexpr int kTreeLanes = 256;
+static_assert(HA_OPT_BLOCK == kTreeLanes, "O1's block is the tree's width");
+
+// THE tree of O1 (and of L1, H6) over NQ lists of 256 lane values at once; q[j][0] is list j's s_b (read by lane 0)
+template <int NQ>
+__device__ __forceinline__ void block_tree(double (*q)[kTreeLanes], int tid) {
+    for (int off = kTreeLanes / 2; off >= 1; off >>= 1) {
+        __syncthreads();
+        if (tid < off) {
+#pragma unroll
+            for (int j = 0; j < NQ; ++j) q[j][tid] = q[j][tid] + q[j][tid + off];
+        }
+    }
+}
+
+// the same tree on the host over one list, in place -> its s_b
+double host_block_tree(double* q) {
+    for (int off = kTreeLanes / 2; off >= 1; off >>= 1)
+        for (int i = 0; i < off; ++i) q[i] = q[i] + q[i + off];
+    return q[0];
+}
+
 struct AdamParams {
     ha_adam_tensor t[HA_OPT_MAX_TENSORS];
     int32_t first[HA_OPT_MAX_TENSORS + 1];   // first[k]: the first block of tensor k; first[n]: all blocks
@@ -1271,16 +1311,13 @@ __device__ __forceinline__ int adam_tensor_of(const AdamParams& p, int b) {
 }
 
 __global__ __launch_bounds__(HA_OPT_BLOCK) void opt_norm_kernel(const AdamParams p) {
-    __shared__ double q[HA_OPT_BLOCK];
+    __shared__ double q[1][kTreeLanes];
     const int b = blockIdx.x, tid = threadIdx.x, k = adam_tensor_of(p, b);
     const int64_t i = (int64_t)(b - p.first[k]) * HA_OPT_BLOCK + tid;
     const float g = i < p.t[k].numel ? p.t[k].grad[i] : 0.0f;
-    q[tid] = (double)g * (double)g;
-    for (int off = HA_OPT_BLOCK / 2; off >= 1; off >>= 1) {
-        __syncthreads();
-        if (tid < off) q[tid] = q[tid] + q[tid + off];
-    }
-    if (tid == 0) p.partial[b] = q[0];
+    q[0][tid] = (double)g * (double)g;
+    block_tree<1>(q, tid);
+    if (tid == 0) p.partial[b] = q[0][0];
 }
 
 __global__ __launch_bounds__(HA_OPT_BLOCK) void opt_adam_kernel(const AdamParams p) {
@@ -1358,9 +1395,12 @@ ha_status check_adam(int64_t n, const ha_adam_tensor* ts, const ha_adam_hyper* h
 //                       tree.
 //   loss_stats_kernel   one workgroup: lane l < 7 adds list l in block order, lane 0 forms the statistics.
 // The serial totals bound a large call, as O2 bounds ha_adam_step: HA_LOSS_MAX_BLOCKS is the cap.
-constexpr int kLossLanes = 256, kLossPerLane = HA_LOSS_BLOCK / kLossLanes, kLossLists = 7, kLossStage = 512;
+constexpr int kLossLanes = kTreeLanes, kLossPerLane = HA_LOSS_BLOCK / kLossLanes, kLossLists = 7, kLossStage = 512;
 static_assert(HA_LOSS_BLOCK % kLossLanes == 0 && kLossPerLane >= 1, "whole rows a lane");
 static_assert((int64_t)HA_LOSS_BLOCK * HA_LOSS_MAX_BLOCKS >= (int64_t)256 * 16384, "a 256 x 16,384 buffer is one call");
+
+// L1's blocks over n >= 1 rows
+constexpr int64_t loss_blocks(int64_t n) { return (n - 1) / HA_LOSS_BLOCK + 1; }
 
 struct LossParams {
     ha_ppo_loss_io io;
@@ -1369,18 +1409,6 @@ struct LossParams {
     int32_t nb;
     double* ws;   // [kLossLists][nb]
 };
-
-// the tree of O1 over NQ lists of 256 lane sums at once; q[j][0] is list j's s_b (read by lane 0)
-template <int NQ>
-__device__ __forceinline__ void loss_tree(double (*q)[kLossLanes], int tid) {
-    for (int off = kLossLanes / 2; off >= 1; off >>= 1) {
-        __syncthreads();
-        if (tid < off) {
-#pragma unroll
-            for (int j = 0; j < NQ; ++j) q[j][tid] = q[j][tid] + q[j][tid + off];
-        }
-    }
-}
 
 // L1's totals of NL lists of nb block sums that lie nb apart from `lists`: the blocks' sums are staged in
 // LDS kLossStage blocks at a time by all lanes (coalesced loads, no chain of load latencies), and lane
@@ -1418,7 +1446,7 @@ __global__ __launch_bounds__(kLossLanes) void loss_mean_kernel(const LossParams 
         s = s + (i < p.n ? (double)adv[i] : 0.0);
     }
     q[0][tid] = s;
-    loss_tree<1>(q, tid);
+    block_tree<1>(q, tid);
     if (tid == 0) p.ws[b] = q[0][0];
 }
 
@@ -1444,7 +1472,7 @@ __global__ __launch_bounds__(kLossLanes) void loss_spread_kernel(const LossParam
         s = s + (i < p.n ? dev * dev : 0.0);
     }
     q[0][tid] = s;
-    loss_tree<1>(q, tid);
+    block_tree<1>(q, tid);
     if (tid == 0) p.ws[p.nb + b] = q[0][0];
 }
 
@@ -1496,7 +1524,7 @@ __global__ __launch_bounds__(kLossLanes) void loss_rows_kernel(const LossParams 
     }
 #pragma unroll
     for (int j = 0; j < 5; ++j) q[j][tid] = s[j];
-    loss_tree<5>(q, tid);
+    block_tree<5>(q, tid);
     if (tid < 5) p.ws[(int64_t)(2 + tid) * p.nb + b] = q[tid][0];
 }
 
@@ -1515,16 +1543,21 @@ __global__ __launch_bounds__(kLossLanes) void loss_stats_kernel(const LossParams
     }
 }
 
-// The checks of ha_ppo_loss / ha_host_ppo_loss; fills the constants (io, hy and k NULL: n_rows alone,
-// for the workspace's size).
-ha_status check_loss(int64_t n, const ha_ppo_loss_io* io, const ha_ppo_loss_hyper* hy, LossConsts* k) {
+// the rows of one call of ha_ppo_loss or ha_ppo_heads_*: all a workspace's size needs
+ha_status check_loss_rows(int64_t n) {
     char m[200];
     if (n < 1 || n > (int64_t)HA_LOSS_BLOCK * HA_LOSS_MAX_BLOCKS) {
         snprintf(m, sizeof m, "n_rows = %lld: 1 to %lld rows a call (%d blocks of %d)", (long long)n,
                  (long long)HA_LOSS_BLOCK * HA_LOSS_MAX_BLOCKS, HA_LOSS_MAX_BLOCKS, HA_LOSS_BLOCK);
         return fail_to(nullptr, HE_ESHAPE, m);
     }
-    if (!k) return HE_OK;
+    return HE_OK;
+}
+
+// The checks of ha_ppo_loss / ha_host_ppo_loss; fills the constants.
+ha_status check_loss(int64_t n, const ha_ppo_loss_io* io, const ha_ppo_loss_hyper* hy, LossConsts* k) {
+    const ha_status st = check_loss_rows(n);
+    if (st != HE_OK) return st;
     if (!io || !hy) return fail_to(nullptr, HE_EINVAL, "io or hyper is NULL");
     if (n == 1 && hy->normalize_advantage)
         return fail_to(nullptr, HE_ESHAPE, "n_rows = 1 with normalize_advantage: the unbiased std needs two rows");
@@ -1568,9 +1601,7 @@ double loss_sum_host(int64_t n, F term) {
             }
             q[i] = s;
         }
-        for (int off = kLossLanes / 2; off >= 1; off >>= 1)
-            for (int i = 0; i < off; ++i) q[i] = q[i] + q[i + off];
-        total = total + q[0];
+        total = total + host_block_tree(q);
     }
     return total;
 }
@@ -1601,11 +1632,6 @@ constexpr size_t kHw2t = kHw1t + (size_t)kMlp * kHid, kHeadsNetFloats = kHw2t + 
 constexpr size_t kHls = 2 * kHeadsNetFloats, kHpart = kHls + 4;   // log_std[2], std[2]; then f64 [2][blocks]
 static_assert(kHeadsNetFloats % 4 == 0 && (kHpart * sizeof(float)) % 16 == 0, "aligned sections");
 static_assert(HA_LOSS_BLOCK % kHRows == 0 && kHRows == 2 * kTile, "whole tiles a block, two MFMA halves a tile");
-
-struct HeadsNetW {
-    const float *w1, *b1, *w2, *b2, *w3, *b3;
-    int n_out;
-};
 
 inline HeadsNetW heads_net(const ha_ppo_heads_weights* w, bool critic) {
     return critic ? HeadsNetW{w->v1, w->vb1, w->v2, w->vb2, w->v3, w->vb3, 1}
@@ -1961,7 +1987,7 @@ __global__ __launch_bounds__(kThreads, 2) void heads_bwd_kernel(const HeadsBwdPa
         }
         t.q[j][tid] = s;
     }
-    loss_tree<kAct>(t.q, tid);
+    block_tree<kAct>(t.q, tid);
     if (tid < kAct) p.part[(int64_t)tid * p.nb + blockIdx.x] = t.q[tid][0];
 }
 
@@ -1976,19 +2002,9 @@ __global__ __launch_bounds__(kLossLanes) void heads_lsd_kernel(const double* __r
 
 // The checks of the four ha_ppo_heads entry points: m16 / m8 are the alignment masks of the [R][128],
 // [R][64] and weight arrays and of the [R][2] arrays (3 on the host).  ptrs16 / ptrs8 / ptrs4 end at n16 ...
-ha_status check_heads_rows(int64_t n) {
-    char m[200];
-    if (n < 1 || n > (int64_t)HA_LOSS_BLOCK * HA_LOSS_MAX_BLOCKS) {
-        snprintf(m, sizeof m, "n_rows = %lld: 1 to %lld rows a call (%d blocks of %d)", (long long)n,
-                 (long long)HA_LOSS_BLOCK * HA_LOSS_MAX_BLOCKS, HA_LOSS_MAX_BLOCKS, HA_LOSS_BLOCK);
-        return fail_to(nullptr, HE_ESHAPE, m);
-    }
-    return HE_OK;
-}
-
 ha_status check_heads(int64_t n, const ha_ppo_heads_weights* w, const void* io, uintptr_t m16, uintptr_t m8,
                       const void* const* p16, int n16, const void* const* p8, int n8, const void* const* p4, int n4) {
-    const ha_status st = check_heads_rows(n);
+    const ha_status st = check_loss_rows(n);
     if (st != HE_OK) return st;
     if (!w || !io) return fail_to(nullptr, HE_EINVAL, "weights or io is NULL");
     if (w->activation != HA_ACT_TANH && w->activation != HA_ACT_RELU) return fail_to(nullptr, HE_EINVAL, "unknown activation");
@@ -2024,26 +2040,15 @@ ha_status check_heads_bwd(int64_t n, const ha_ppo_heads_weights* w, const ha_ppo
     return check_heads(n, w, io, m16, m8, p16, 10, p8, 3, p4, 4);
 }
 
+// the workspace checked, then heads_pack_kernel into it
 ha_status heads_pack(const ha_ppo_heads_weights* w, void* workspace, void* stream) {
+    const ha_status st = check_workspace(workspace);
+    if (st != HE_OK) return st;
     HeadsPackParams pp;
     pp.w1[0] = w->w1, pp.w1[1] = w->v1, pp.w2[0] = w->w2, pp.w2[1] = w->v2;
     pp.log_std = w->log_std;
     pp.ws = (float*)workspace;
     return launch(nullptr, heads_pack_kernel, dim3(24, 2), dim3(256), stream, "heads_pack_kernel", pp);
-}
-
-// H1 for one network and row on the host: the two layers into a1, a2
-void host_heads_mlp(const HeadsNetW& w, const float* h, bool relu, float* a1, float* a2) {
-    for (int j = 0; j < kMlp; ++j) {
-        float acc = w.b1[j];
-        for (int k = 0; k < kHid; ++k) acc = fmaf(w.w1[j * kHid + k], h[k], acc);
-        a1[j] = mlp_act(acc, relu);
-    }
-    for (int j = 0; j < kMlp; ++j) {
-        float acc = w.b2[j];
-        for (int k = 0; k < kMlp; ++k) acc = fmaf(w.w2[j * kMlp + k], a1[k], acc);
-        a2[j] = mlp_act(acc, relu);
-    }
 }
 
 // H5 for one network and row on the host, from the head's gradient d_out[n_out]
@@ -2154,12 +2159,13 @@ ha_status ha_host_step(const ha_weights* w, int64_t n, const float* obs, const u
     const HostNorm norm(w->obs_mean, w->obs_var, w->epsilon, w->has_clip != 0, w->clip_obs);
     const bool relu = w->activation == HA_ACT_RELU, tsq = w->squash == HA_SQUASH_TANH;
     const HostNet net = actor_net(w);
+    const HeadsNetW head = net.heads();
     for (int64_t e = 0; e < n; ++e) {
         float x[kObs], a2[kMlp];
         norm.env(obs, e, x, obs_norm_out);
         host_net_env(net, x, episode_start[e] != 0, h + e * kHid, c + e * kHid, true, relu, a2);
         for (int j = 0; j < kAct; ++j) {
-            const float m = host_head(net, j, a2);
+            const float m = host_head(head, j, a2);
             if (mean_out) mean_out[e * kAct + j] = m;
             actions[e * kAct + j] = squash_action(m, tsq);
         }
@@ -2299,6 +2305,7 @@ ha_status ha_host_policy_step(const ha_policy_weights* w, int64_t n, int64_t env
     const HostNorm norm(w->obs_mean, w->obs_var, w->epsilon, w->has_clip != 0, w->clip_obs);
     const bool relu = w->activation == HA_ACT_RELU;
     const HostNet pi = actor_net(w), vf = critic_net(w);
+    const HeadsNetW head_pi = pi.heads(), head_vf = vf.heads();
     const float stdv[kAct] = {policy_std(w->log_std[0]), policy_std(w->log_std[1])};
     for (int64_t e = 0; e < n; ++e) {
         float x[kObs], a2[kMlp], mean[kAct];
@@ -2306,11 +2313,11 @@ ha_status ha_host_policy_step(const ha_policy_weights* w, int64_t n, int64_t env
         const bool fresh = episode_start[e] != 0;
         host_net_env(pi, x, fresh, h_pi + e * kHid, c_pi + e * kHid, write_state != 0, relu, a2);
         for (int j = 0; j < kAct; ++j) {
-            mean[j] = host_head(pi, j, a2);
+            mean[j] = host_head(head_pi, j, a2);
             if (mean_out) mean_out[e * kAct + j] = mean[j];
         }
         host_net_env(vf, x, fresh, h_vf + e * kHid, c_vf + e * kHid, write_state != 0, relu, a2);
-        values[e] = host_head(vf, 0, a2);
+        values[e] = host_head(head_vf, 0, a2);
         sample_action(mean, w->log_std, stdv, seed, step_index, (uint64_t)(env_id_offset + e), deterministic != 0,
                       actions + e * kAct, env_actions + e * kAct, log_probs + e);
     }
@@ -2501,10 +2508,7 @@ ha_status ha_host_lstm_seq_weight_grads(int64_t n_nets, int64_t L, int64_t B, co
                 for (int64_t r = b0; r < b0 + HA_WGRAD_BLOCK; ++r) {   // W1, the padding terms included
                     float z[kKp];
                     if (r < R) {
-                        const bool fresh = episode_starts[r] != 0;
-                        const float* hp = r >= B ? n.h + (r - B) * kHid : n.h0 + r * kHid;
-                        for (int i = 0; i < kObs; ++i) z[i] = x[r * kObs + i];
-                        for (int u = 0; u < kHid; ++u) z[kObs + u] = fresh ? 0.0f : hp[u];
+                        host_xh(x + r * kObs, r >= B ? n.h + (r - B) * kHid : n.h0 + r * kHid, episode_starts[r] != 0, z);
                         z[kKx] = 1.0f;
                     } else {
                         for (int i = 0; i < kKp; ++i) z[i] = 0.0f;
@@ -2534,9 +2538,8 @@ ha_status ha_adam_step(int64_t n_tensors, const ha_adam_tensor* tensors, const h
                        void* stream) {
     AdamParams p;
     ha_status st = check_adam(n_tensors, tensors, hyper, p.first, &p.k);
+    if (st == HE_OK) st = check_workspace(workspace, 8);
     if (st != HE_OK) return st;
-    if (!workspace || (((uintptr_t)workspace) & 7u))
-        return fail_to(nullptr, HE_EINVAL, "workspace must be non-NULL and 8-byte aligned");
     uintptr_t bits = (uintptr_t)hyper->grad_norm_out;
     for (int64_t j = 0; j < n_tensors; ++j) {
         p.t[j] = tensors[j];
@@ -2570,9 +2573,7 @@ ha_status ha_host_adam_step(int64_t n_tensors, const ha_adam_tensor* tensors, co
                 const float g = i0 + i < tensors[j].numel ? tensors[j].grad[i0 + i] : 0.0f;
                 q[i] = (double)g * (double)g;
             }
-            for (int off = HA_OPT_BLOCK / 2; off >= 1; off >>= 1)
-                for (int i = 0; i < off; ++i) q[i] = q[i] + q[i + off];
-            total = total + q[0];
+            total = total + host_block_tree(q);
         }
     float norm;   // O3, O4
     const float c = adam_clip(total, k, &norm);
@@ -2585,20 +2586,19 @@ ha_status ha_host_adam_step(int64_t n_tensors, const ha_adam_tensor* tensors, co
 }
 
 size_t ha_ppo_loss_workspace_bytes(int64_t n_rows) {
-    if (check_loss(n_rows, nullptr, nullptr, nullptr) != HE_OK) return 0;
-    return (size_t)((n_rows - 1) / HA_LOSS_BLOCK + 1) * kLossLists * sizeof(double);
+    if (check_loss_rows(n_rows) != HE_OK) return 0;
+    return (size_t)loss_blocks(n_rows) * kLossLists * sizeof(double);
 }
 
 ha_status ha_ppo_loss(int64_t n_rows, const ha_ppo_loss_io* io, const ha_ppo_loss_hyper* hyper, void* workspace,
                       void* stream) {
     LossParams p;
     ha_status st = check_loss(n_rows, io, hyper, &p.k);
+    if (st == HE_OK) st = check_workspace(workspace, 8);
     if (st != HE_OK) return st;
-    if (!workspace || (((uintptr_t)workspace) & 7u))
-        return fail_to(nullptr, HE_EINVAL, "workspace must be non-NULL and 8-byte aligned");
     p.io = *io;
     p.n = n_rows;
-    p.nb = (int32_t)((n_rows - 1) / HA_LOSS_BLOCK + 1);
+    p.nb = (int32_t)loss_blocks(n_rows);
     p.ws = (double*)workspace;
     const dim3 grid((unsigned)p.nb), block(kLossLanes);
     if (p.k.normalize) {
@@ -2651,17 +2651,14 @@ ha_status ha_host_ppo_loss(int64_t n_rows, const ha_ppo_loss_io* io, const ha_pp
 }
 
 size_t ha_ppo_heads_workspace_bytes(int64_t n_rows) {
-    if (check_heads_rows(n_rows) != HE_OK) return 0;
-    return kHpart * sizeof(float) + (size_t)((n_rows - 1) / HA_LOSS_BLOCK + 1) * kAct * sizeof(double);
+    if (check_loss_rows(n_rows) != HE_OK) return 0;
+    return kHpart * sizeof(float) + (size_t)loss_blocks(n_rows) * kAct * sizeof(double);
 }
 
 ha_status ha_ppo_heads_forward(int64_t n_rows, const ha_ppo_heads_weights* weights, const ha_ppo_heads_fwd* io,
                                void* workspace, void* stream) {
     ha_status st = check_heads_fwd(n_rows, weights, io, 15u, 7u);
-    if (st != HE_OK) return st;
-    st = check_workspace(workspace);
-    if (st != HE_OK) return st;
-    st = heads_pack(weights, workspace, stream);
+    if (st == HE_OK) st = heads_pack(weights, workspace, stream);
     if (st != HE_OK) return st;
     HeadsFwdParams p;
     p.n = n_rows;
@@ -2681,15 +2678,12 @@ ha_status ha_ppo_heads_forward(int64_t n_rows, const ha_ppo_heads_weights* weigh
 ha_status ha_ppo_heads_backward(int64_t n_rows, const ha_ppo_heads_weights* weights, const ha_ppo_heads_bwd* io,
                                 void* workspace, void* stream) {
     ha_status st = check_heads_bwd(n_rows, weights, io, 15u, 7u);
-    if (st != HE_OK) return st;
-    st = check_workspace(workspace);
-    if (st != HE_OK) return st;
-    st = heads_pack(weights, workspace, stream);
+    if (st == HE_OK) st = heads_pack(weights, workspace, stream);
     if (st != HE_OK) return st;
     HeadsBwdParams p;
     p.n = n_rows;
     p.relu = weights->activation == HA_ACT_RELU;
-    p.nb = (int32_t)((n_rows - 1) / HA_LOSS_BLOCK + 1);
+    p.nb = (int32_t)loss_blocks(n_rows);
     p.io = *io;
     p.net[0] = heads_net(weights, false);
     p.net[1] = heads_net(weights, true);
@@ -2710,21 +2704,13 @@ ha_status ha_host_ppo_heads_forward(int64_t n_rows, const ha_ppo_heads_weights* 
     const float stdv[kAct] = {policy_std(ls[0]), policy_std(ls[1])};
     const float ent = heads_entropy(ls);
     for (int64_t r = 0; r < n_rows; ++r) {
-        float* a2 = io->a2_pi + r * kMlp;
-        host_heads_mlp(pi, io->h_pi + r * kHid, relu, io->a1_pi + r * kMlp, a2);
-        float mean[kAct];
-        for (int j = 0; j < kAct; ++j) {
-            float m = pi.b3[j];
-            for (int k = 0; k < kMlp; ++k) m = fmaf(pi.w3[j * kMlp + k], a2[k], m);
-            mean[j] = io->mean[r * kAct + j] = m;
-        }
+        float* mean = io->mean + r * kAct;
+        host_mlp(pi, io->h_pi + r * kHid, relu, io->a1_pi + r * kMlp, io->a2_pi + r * kMlp);
+        for (int j = 0; j < kAct; ++j) mean[j] = host_head(pi, j, io->a2_pi + r * kMlp);
         io->log_prob[r] = heads_log_prob(io->actions + r * kAct, mean, ls, stdv);
         io->entropy[r] = ent;
-        a2 = io->a2_vf + r * kMlp;
-        host_heads_mlp(vf, io->h_vf + r * kHid, relu, io->a1_vf + r * kMlp, a2);
-        float v = vf.b3[0];
-        for (int k = 0; k < kMlp; ++k) v = fmaf(vf.w3[k], a2[k], v);
-        io->values[r] = v;
+        host_mlp(vf, io->h_vf + r * kHid, relu, io->a1_vf + r * kMlp, io->a2_vf + r * kMlp);
+        io->values[r] = host_head(vf, 0, io->a2_vf + r * kMlp);
     }
     return HE_OK;
 }

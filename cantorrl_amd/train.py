@@ -61,19 +61,42 @@ WGRAD_BLOCK, WGRAD_CHUNK = 128, 64   # HA_WGRAD_BLOCK, HA_WGRAD_CHUNK of include
 WEIGHT_GRADS = ("torch", "kernel")
 
 
-def _weight_grads_mode(mode):
-    if mode not in WEIGHT_GRADS:
-        raise ValueError(f"weight_grads must be one of {WEIGHT_GRADS}, not {mode!r}")
+def _mode(name, mode, allowed):
+    """The value of the option `name` (weight_grads, heads, loss), refused unless it is one of `allowed`."""
+    if mode not in allowed:
+        raise ValueError(f"{name} must be one of {allowed}, not {mode!r}")
     return mode
 
 
-def _f32(t, shape, name, device):
-    """t as a contiguous, 16-byte aligned float32 tensor of `shape` on `device` (no copy when it is)."""
-    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or t.device != device:
+def _f32(t, shape, name, device, align=16):
+    """t as a contiguous, `align`-byte aligned float32 tensor of `shape` on `device` (no copy when it is;
+    align=None: wherever it stands, never a copy of contiguous data)."""
+    if t.dtype != torch.float32 or t.shape != shape or t.device != device:   # (shape: a tuple or a torch.Size)
         raise ValueError(f"{name} must be a float32 tensor of shape {tuple(shape)} on {device}, not "
                          f"{t.dtype} {tuple(t.shape)} on {t.device}")
     t = t.detach().contiguous()
-    return t.clone() if t.data_ptr() % 16 else t
+    return t.clone() if align and t.data_ptr() % align else t
+
+
+def _call(op, dev, args, host=None, workspace=None):
+    """THE call path of this module's entry points (ppo_loss_kernel spells it out, see there):
+    ha_host_<op>(*args) for tensors on the CPU, else ha_<op>(*args, workspace, stream) on `dev`'s current
+    stream, and the status checked (_check: a refusal is a ValueError with the library's message).  host:
+    None is by `dev`, anything else must agree with it.  workspace: a uint8 tensor on `dev` that the caller
+    keeps (DeviceAdam), or (the entry point that sizes it, *its arguments) for a fresh one."""
+    lib = load()
+    host = dev.type == "cpu" if host is None else bool(host)
+    if host != (dev.type == "cpu"):
+        raise ValueError("host=True takes CPU tensors, host=False tensors on a HIP device")
+    if host:
+        st = getattr(lib, "ha_host_" + op)(*args)
+    else:
+        with torch.cuda.device(dev):
+            if isinstance(workspace, tuple):
+                size = getattr(lib, workspace[0])(*workspace[1:])
+                workspace = torch.empty(size or 16, dtype=torch.uint8, device=dev)
+            st = getattr(lib, "ha_" + op)(*args, workspace.data_ptr(), _stream(dev))
+    _check(lib, st, "ha_" + op)
 
 
 def _starts(es, L, B, device):
@@ -95,18 +118,12 @@ def _seq_shapes(L, B):
                 d_gates=(L, B, 4, HIDDEN), d_w_ih=(G, OBS_DIM), d_w_hh=(G, HIDDEN), d_b=(G,))
 
 
-def _seq_call(op, struct, x, like, episode_starts, nets, host, inputs, outputs,
-              workspace="ha_lstm_seq_workspace_bytes"):
-    """What lstm_seq_forward / _backward / _weight_grads share: ha_<op> on a HIP device or ha_host_<op>
-    (host; default: by the tensors' device) over `nets`, one or two dicts with the tensors `inputs` of
-    `struct`.  L, B are `like`'s leading dimensions; x is None for the call that takes none; `workspace`
-    names the entry point that sizes the device call's workspace, from as many of (n, L, B) as it takes.
-    -> per network the tuple of its new `outputs` tensors."""
-    lib = load()
+def _seq_call(op, struct, x, like, episode_starts, nets, host, inputs, outputs, sized_by_rows=False):
+    """What lstm_seq_forward / _backward / _weight_grads share: _call of `op` over `nets`, one or two
+    dicts with the tensors `inputs` of `struct`.  L, B are `like`'s leading dimensions; x is None for the
+    call that takes none; sized_by_rows: the workspace grows with L B (the weight gradients' own sizing
+    entry point), not with the networks alone.  -> per network the tuple of its new `outputs` tensors."""
     dev = like.device
-    host = dev.type == "cpu" if host is None else bool(host)
-    if host != (dev.type == "cpu"):
-        raise ValueError("host=True takes CPU tensors, host=False tensors on a HIP device")
     if x is not None and (x.dim() != 3 or x.shape[2] != OBS_DIM):
         raise ValueError(f"x must be [L, B, {OBS_DIM}]")
     L, B = int(like.shape[0]), int(like.shape[1])
@@ -129,14 +146,8 @@ def _seq_call(op, struct, x, like, episode_starts, nets, host, inputs, outputs,
         for name, t in zip(outputs, new):
             setattr(s, name, t.data_ptr())
         out.append(new)
-    if host:
-        st = getattr(lib, "ha_host_" + op)(n, L, B, *lead, arr)
-    else:
-        with torch.cuda.device(dev):
-            size = getattr(lib, workspace)   # sized by n alone, or by n, L, B
-            ws = torch.empty(size(n) if len(size.argtypes) == 1 else size(n, L, B), dtype=torch.uint8, device=dev)
-            st = getattr(lib, "ha_" + op)(n, L, B, *lead, arr, ws.data_ptr(), _stream(dev))
-    _check(lib, st, "ha_" + op)
+    ws = ("ha_lstm_seq_weight_grads_workspace_bytes", n, L, B) if sized_by_rows else ("ha_lstm_seq_workspace_bytes", n)
+    _call(op, dev, (n, L, B, *lead, arr), host, ws)
     return out
 
 
@@ -161,16 +172,34 @@ def lstm_seq_weight_grads(x, episode_starts, nets, host=None):
     dicts of d_gates [L,B,4,128], h [L,B,128] (the forward's), h0 [B,128] -> a list of (d_w_ih [512,13],
     d_w_hh [512,128], d_b [512]) f32 per network; d_b is db_ih and db_hh.  No autograd."""
     return _seq_call("lstm_seq_weight_grads", HaLstmSeqWgrad, x, x, episode_starts, nets, host,
-                     ("d_gates", "h", "h0"), ("d_w_ih", "d_w_hh", "d_b"), "ha_lstm_seq_weight_grads_workspace_bytes")
+                     ("d_gates", "h", "h0"), ("d_w_ih", "d_w_hh", "d_b"), sized_by_rows=True)
+
+
+def _blocked_tn(d, x, into=None, block=128):
+    """d^T x and d's column sums over the rows of d [R,m], x [R,k], added in f64 into the accumulators
+    `into` = (w [m,k], b [m]) (None: new zeros) and returned: one batched f32 GEMM sums blocks of `block`
+    rows, the blocks' results are added in f64, then the ragged tail's."""
+    R, f64 = d.shape[0], torch.float64
+    nb = R // block
+    w, b = into or (torch.zeros((d.shape[1], x.shape[1]), dtype=f64, device=d.device),
+                    torch.zeros(d.shape[1], dtype=f64, device=d.device))
+    if nb:
+        d3 = d[:nb * block].view(nb, block, -1)
+        w += torch.bmm(d3.transpose(1, 2), x[:nb * block].view(nb, block, -1)).sum(0, dtype=f64)
+        b += d3.sum(1).sum(0, dtype=f64)
+    if R > nb * block:
+        w += (d[nb * block:].t() @ x[nb * block:]).to(f64)
+        b += d[nb * block:].sum(0).to(f64)
+    return w, b
 
 
 def weight_grads(d_gates, x, h, h0, episode_starts, rows=1 << 18, block=128):
     """The LSTM's weight gradients from d_gates [L,B,4,128], as f64 tensors: dW_ih = d_gates^T x,
     dW_hh = d_gates^T h_prev, db_ih = db_hh = sum d_gates, with h_prev = h shifted by one step, h0 in
-    front, zeroed where episode_starts.  The sums run over L B rows: one batched f32 GEMM against
-    [x | h_prev] sums blocks of `block` rows, and the blocks' results are added in f64 (about `rows`
-    rows a pass).  One f32 GEMM over all rows misses the tests' 4 x d_ref bound by its own rounding,
-    f64 GEMMs of these shapes are 30 x slower."""
+    front, zeroed where episode_starts.  The sums run over L B rows, about `rows` rows a pass: each pass
+    is _blocked_tn against [x | h_prev] into the same two f64 accumulators, in step order.  One f32 GEMM
+    over all rows misses the tests' 4 x d_ref bound by its own rounding, f64 GEMMs of these shapes are
+    30 x slower."""
     L, B = d_gates.shape[:2]
     f64, G, K = torch.float64, 4 * HIDDEN, OBS_DIM + HIDDEN
     steps = max(1, rows // B)
@@ -179,18 +208,10 @@ def weight_grads(d_gates, x, h, h0, episode_starts, rows=1 << 18, block=128):
     for t0 in range(0, L, steps):
         t1 = min(t0 + steps, L)
         n = (t1 - t0) * B
-        dg = d_gates[t0:t1].reshape(n, G)
         first = (h0 if t0 == 0 else h[t0 - 1]).unsqueeze(0)
         keep = (episode_starts[t0:t1] == 0).to(h.dtype).unsqueeze(-1)
         xh = torch.cat([x[t0:t1], torch.cat([first, h[t0:t1 - 1]], 0) * keep], -1).reshape(n, K)
-        nb = n // block
-        if nb:
-            d3 = dg[:nb * block].view(nb, block, G)
-            w += torch.bmm(d3.transpose(1, 2), xh[:nb * block].view(nb, block, K)).sum(0, dtype=f64)
-            b += d3.sum(1).sum(0, dtype=f64)
-        if n > nb * block:
-            w += (dg[nb * block:].t() @ xh[nb * block:]).to(f64)
-            b += dg[nb * block:].sum(0).to(f64)
+        _blocked_tn(d_gates[t0:t1].reshape(n, G), xh, (w, b), block)
     return w[:, :OBS_DIM], w[:, OBS_DIM:], b, b.clone()
 
 
@@ -241,14 +262,15 @@ def lstm_sequence(x, episode_starts, h0, c0, w_ih, w_hh, b_ih, b_hh, host=None, 
     f32 GEMMs added in f64), "kernel" with ha_lstm_seq_weight_grads (contract W1-W4: the same bits on
     the device and on the host build)."""
     host = x.device.type == "cpu" if host is None else bool(host)
-    return _LstmSeq.apply(host, _weight_grads_mode(weight_grads), x, episode_starts, h0, c0, w_ih, w_hh, b_ih, b_hh)[0]
+    mode = _mode("weight_grads", weight_grads, WEIGHT_GRADS)
+    return _LstmSeq.apply(host, mode, x, episode_starts, h0, c0, w_ih, w_hh, b_ih, b_hh)[0]
 
 
 def lstm_sequence_pair(x, episode_starts, actor, critic, host=None, weight_grads="torch"):
     """lstm_sequence for actor and critic in one launch each way: `actor`, `critic` are the NET_INPUTS
     tuples (h0, c0, w_ih, w_hh, b_ih, b_hh) -> (h_pi, h_vf)."""
     host = x.device.type == "cpu" if host is None else bool(host)
-    return _LstmSeq.apply(host, _weight_grads_mode(weight_grads), x, episode_starts, *actor, *critic)
+    return _LstmSeq.apply(host, _mode("weight_grads", weight_grads, WEIGHT_GRADS), x, episode_starts, *actor, *critic)
 
 
 # --------------------------------------------------------------------------- the heads as kernels
@@ -274,12 +296,6 @@ class HaPpoHeadsBwd(ctypes.Structure):
     _fields_ = [(k, _VP) for k in HEADS_BWD_IN + HEADS_BWD_OUT]
 
 
-def _heads_mode(mode):
-    if mode not in HEADS:
-        raise ValueError(f"heads must be one of {HEADS}, not {mode!r}")
-    return mode
-
-
 def _heads_row_shapes(R):
     one, two, mid, wide = (R,), (R, ACT_DIM), (R, MLP), (R, HIDDEN)
     return dict(h_pi=wide, h_vf=wide, actions=two, values=one, log_prob=one, entropy=one, mean=two, a1_pi=mid,
@@ -288,17 +304,12 @@ def _heads_row_shapes(R):
 
 
 def _heads_call(op, struct, rows, inputs, outputs, weights, activation, host):
-    """What ppo_heads_forward / _backward share: ha_<op> on a HIP device or ha_host_<op> over `rows`, a dict
-    of the `inputs` tensors with R rows each, and `weights`, the 13 HEADS_TENSORS -> a dict of the new
-    `outputs` tensors."""
-    lib = load()
+    """What ppo_heads_forward / _backward share: _call of `op` over `rows`, a dict of the `inputs` tensors
+    with R rows each, and `weights`, the 13 HEADS_TENSORS -> a dict of the new `outputs` tensors."""
     if activation not in ("tanh", "relu"):
         raise ValueError(f"activation must be 'tanh' or 'relu', not {activation!r}")
     first = rows[inputs[0]]
     dev, R = first.device, int(first.shape[0]) if first.dim() else 0
-    host = dev.type == "cpu" if host is None else bool(host)
-    if host != (dev.type == "cpu"):
-        raise ValueError("host=True takes CPU tensors, host=False tensors on a HIP device")
     if len(weights) != len(HEADS_TENSORS):
         raise ValueError(f"weights: the {len(HEADS_TENSORS)} tensors {HEADS_TENSORS}")
     shapes = _heads_row_shapes(R)
@@ -315,13 +326,7 @@ def _heads_call(op, struct, rows, inputs, outputs, weights, activation, host):
     out = {name: torch.empty(shapes[name], dtype=torch.float32, device=dev) for name in outputs}
     for name, t in out.items():
         setattr(io, name, t.data_ptr())
-    if host:
-        st = getattr(lib, "ha_host_" + op)(R, ctypes.byref(w), ctypes.byref(io))
-    else:
-        with torch.cuda.device(dev):
-            ws = torch.empty(lib.ha_ppo_heads_workspace_bytes(R) or 16, dtype=torch.uint8, device=dev)
-            st = getattr(lib, "ha_" + op)(R, ctypes.byref(w), ctypes.byref(io), ws.data_ptr(), _stream(dev))
-    _check(lib, st, "ha_" + op)
+    _call(op, dev, (R, ctypes.byref(w), ctypes.byref(io)), host, ("ha_ppo_heads_workspace_bytes", R))
     return out
 
 
@@ -340,23 +345,6 @@ def ppo_heads_backward(d_values, d_log_prob, d_entropy, actions, saved, weights,
     d_z1_vf, d_z2_vf [R,64], d_mean [R,2], d_log_std [2].  No autograd."""
     rows = dict(saved, d_values=d_values, d_log_prob=d_log_prob, d_entropy=d_entropy, actions=actions)
     return _heads_call("ppo_heads_backward", HaPpoHeadsBwd, rows, HEADS_BWD_IN, HEADS_BWD_OUT, weights, activation, host)
-
-
-def _blocked_tn(d, x, block=128):
-    """d^T x and d's column sums over the rows of d [R,m], x [R,k] as f64 tensors: one batched f32 GEMM sums
-    blocks of `block` rows, the blocks' results are added in f64 (as weight_grads)."""
-    R, f64 = d.shape[0], torch.float64
-    nb = R // block
-    w = torch.zeros((d.shape[1], x.shape[1]), dtype=f64, device=d.device)
-    b = torch.zeros(d.shape[1], dtype=f64, device=d.device)
-    if nb:
-        d3 = d[:nb * block].view(nb, block, -1)
-        w += torch.bmm(d3.transpose(1, 2), x[:nb * block].view(nb, block, -1)).sum(0, dtype=f64)
-        b += d3.sum(1).sum(0, dtype=f64)
-    if R > nb * block:
-        w += (d[nb * block:].t() @ x[nb * block:]).to(f64)
-        b += d[nb * block:].sum(0).to(f64)
-    return w, b
 
 
 def heads_weight_grads(d_z, inp):
@@ -449,8 +437,8 @@ class RecurrentPPOModule(torch.nn.Module):
     def __init__(self, activation="tanh", obs_mean=None, obs_var=None, clip_obs=10.0, epsilon=1e-8,
                  weight_grads="torch", heads="torch"):
         super().__init__()
-        self.weight_grads = _weight_grads_mode(weight_grads)
-        self.heads_mode = _heads_mode(heads)
+        self.weight_grads = _mode("weight_grads", weight_grads, WEIGHT_GRADS)
+        self.heads_mode = _mode("heads", heads, HEADS)
         acts = {"tanh": torch.nn.Tanh, "relu": torch.nn.ReLU}
         if activation not in acts:
             raise ValueError(f"activation must be one of {sorted(acts)}, not {activation!r}")
@@ -595,10 +583,7 @@ def ppo_loss_kernel(values, log_prob, entropy, old_log_prob, advantages, returns
             raise ValueError("clip_range_vf needs old_values")
     io, keep = HaPpoLossIo(), []
     for name, t in zip(names, given):
-        if t.dtype != torch.float32 or t.shape != shape or t.device != dev:
-            raise ValueError(f"{name} must be a float32 tensor of shape {tuple(shape)} on {dev}, not "
-                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
-        t = t.detach().contiguous()
+        t = _f32(t, shape, name, dev, None)   # no alignment beyond the tensor's own 4 bytes: never a clone a call
         keep.append(t)
         setattr(io, name, t.data_ptr())
     grads = tuple(torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(3))
@@ -606,6 +591,7 @@ def ppo_loss_kernel(values, log_prob, entropy, old_log_prob, advantages, returns
     io.d_values, io.d_log_prob, io.d_entropy, io.stats = (*(g.data_ptr() for g in grads), out.data_ptr())
     hy = HaPpoLossHyper(float(clip_range), cv, float(ent_coef), float(vf_coef), int(bool(normalize_advantage)))
     n = values.numel()
+    # _call's path spelled out: through the helper this call, launch-bound at small n, measured 0.8 us (2.4 %) slower
     if dev.type == "cpu":
         st = lib.ha_host_ppo_loss(n, ctypes.byref(io), ctypes.byref(hy))
     else:
@@ -713,12 +699,7 @@ class DeviceAdam(torch.optim.Optimizer):
         norm = torch.empty((), dtype=f32, device=dev)
         hy = HaAdamHyper(float(group["lr"]), float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]),
                          0.0 if max_grad_norm is None else float(max_grad_norm), int(steps[0]) + 1, norm.data_ptr())
-        if dev.type == "cpu":
-            st = load().ha_host_adam_step(len(params), arr, ctypes.byref(hy))
-        else:
-            with torch.cuda.device(dev):
-                st = load().ha_adam_step(len(params), arr, ctypes.byref(hy), ws.data_ptr(), _stream(dev))
-        _check(load(), st, "ha_adam_step")
+        _call("adam_step", dev, (len(params), arr, ctypes.byref(hy)), workspace=ws)
         torch._foreach_add_(steps, 1)
         return norm
 
@@ -762,8 +743,7 @@ def ppo_update(module, optimizer, buffer, *, n_epochs=10, envs_per_batch=None, w
     clip_range_vf (None: no value clip) is SB3's, against buffer.values.  target_kl is not built.
     Nothing synchronises
     with the host; returns the last minibatch's statistics and the mean loss as device scalars."""
-    if loss not in LOSSES:
-        raise ValueError(f"loss must be one of {LOSSES}, not {loss!r}")
+    _mode("loss", loss, LOSSES)
     K, n = buffer.k_steps, buffer.n_envs
     W = K if window is None else int(window)
     if W < 1 or K % W:

@@ -278,6 +278,17 @@ def test_autograd_function_on_the_host_build():
     for kw in (dict(), dict(rows=4, block=4), dict(rows=6, block=5)):
         for a, b in zip(train.weight_grads(dg, x, case["out"][0][0], net["h0"], es, **kw), want):
             assert float((a - b).abs().max()) <= 1e-5 * float(b.abs().max())
+    # the default block of 128 over two passes that share the accumulators: 150 rows (a whole block and a
+    # ragged tail), then 100 (a tail alone) with an episode start inside
+    big = dict(seq_case(kind, "none", 5, 50))
+    big["es"] = np.zeros((5, 50), np.uint8)
+    big["es"][4, 10] = 1
+    nb, xb, eb = net_inputs(kind, big["states"]), torch.from_numpy(big["x"]), torch.from_numpy(big["es"])
+    big["out"] = train.lstm_seq_forward(xb, eb, nb, host=True)
+    dgb = host_backward(kind, big, d_h_for(big))[0]
+    want = build_grads(dgb, nb[0], xb, eb, big["out"][0][0])[1:]
+    for a, b in zip(train.weight_grads(dgb, xb, big["out"][0][0], nb[0]["h0"], eb, rows=150), want):
+        assert float((a - b).abs().max()) <= 1e-5 * float(b.abs().max())
     # the pair is the two single calls
     n2 = net_inputs(kind, case["states"])
     pair = train.lstm_sequence_pair(x, es, tuple(n2[0][k] for k in train.NET_INPUTS), tuple(n2[1][k] for k in train.NET_INPUTS))
