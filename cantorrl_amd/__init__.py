@@ -8,6 +8,8 @@ reference's Python interface on top:
 * `HedgingEnv`    -- the single-env gym API with the reference ctor (env.py)
 * `RecurrentActor` -- a RecurrentPPO checkpoint's actor as one HIP kernel (agent.py,
   include/hedge_actor.h, libhedgeactor.so), `HedgingVecEnv.evaluate_actor` around it
+* `StackedRecurrentActor` -- the same for lstm_hidden_size 128 / 256 / 512 and one to four LSTM layers
+  (stack_step_kernel: a tile's layers walked in LDS by H / 32 waves), states [NL, n, H]
 * `RecurrentPolicy`, `RolloutCollector` -- actor + critic + sampling + log-prob per step in one
   kernel and GAE: RecurrentPPO's collect_rollouts on the device (agent.py, collect.py)
 * `lstm_sequence`, `lstm_sequence_pair`, `RecurrentPPOModule`, `ppo_update` -- the LSTM over a stored
@@ -36,6 +38,9 @@ def __getattr__(name):
     if name == "RecurrentActor":
         from .agent import RecurrentActor
         return RecurrentActor
+    if name == "StackedRecurrentActor":
+        from .agent import StackedRecurrentActor
+        return StackedRecurrentActor
     if name == "RecurrentPolicy":
         from .agent import RecurrentPolicy
         return RecurrentPolicy

@@ -5,6 +5,9 @@ per step for every env, the recurrent state resident on the device.
     actor = RecurrentActor.from_sb3_zip("final_model.zip", normalization="normalization_stats.pkl")
     records = venv.evaluate_actor(actor, num_episodes=1000)      # vec_env.HedgingVecEnv
 
+StackedRecurrentActor is the same actor for lstm_hidden_size 128 / 256 / 512 and one to four LSTM
+layers (ha_stack_create, stack_step_kernel), its states [NL, n, H].
+
 RecurrentPolicy is the training-side counterpart: actor and critic (its own LSTM 128 -> 64 -> 64
 -> 1), the sampled action, the value and the log-probability of a rollout step in one launch, and
 GAE; collect.RolloutCollector fills a rollout buffer with it.
@@ -88,8 +91,20 @@ class HaPolicyWeights(ctypes.Structure):
                [(f, _F) for _, f, _ in POLICY_KEYS]
 
 
+STACK_HIDDEN, STACK_MAX_LAYERS = (128, 256, 512), 4   # what ha_stack_create builds (HA_STACK_MAX_LAYERS)
+STACK_LSTM_FIELDS = ("w_ih", "w_hh", "b_ih", "b_hh")  # per layer: lstm_actor.{weight,bias}_{ih,hh}_l{l}
+STACK_LSTM_KEYS = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
+_MLP_KEYS = ACTOR_KEYS[4:]   # w1 .. log_std
+
+
+class HaStackWeights(ctypes.Structure):
+    """ha_stack_weights: ha_weights with one LSTM tensor per layer."""
+    _fields_ = HaWeights._fields_[:12] + [(f, _F * STACK_MAX_LAYERS) for f in STACK_LSTM_FIELDS] + \
+               [(f, _F) for _, f, _ in _MLP_KEYS] + [("obs_mean", _D), ("obs_var", _D)]
+
+
 _vp, _i32, _i64, _u64, _f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double
-_W, _PW = ctypes.POINTER(HaWeights), ctypes.POINTER(HaPolicyWeights)
+_W, _PW, _SW = ctypes.POINTER(HaWeights), ctypes.POINTER(HaPolicyWeights), ctypes.POINTER(HaStackWeights)
 # every entry point of include/hedge_actor.h: symbol -> (restype, argtypes)
 SIG = {
     "ha_version": (ctypes.c_char_p, []),
@@ -99,6 +114,8 @@ SIG = {
     "ha_step": (_i32, [_vp, _i64] + [_vp] * 8),
     "ha_accumulate": (_i32, [_vp, _i64, _i64] + [_vp] * 10 + [_i64, _vp, _vp]),
     "ha_host_step": (_i32, [_W, _i64] + [_vp] * 7),
+    "ha_stack_create": (_i32, [_SW, ctypes.POINTER(_vp)]),
+    "ha_host_stack_step": (_i32, [_SW, _i64] + [_vp] * 7),
     "ha_policy_last_error": (ctypes.c_char_p, [_vp]),
     "ha_policy_create": (_i32, [_PW, ctypes.POINTER(_vp)]),
     "ha_policy_destroy": (_i32, [_vp]),
@@ -180,6 +197,54 @@ def weights_from_state_dict(sd):
     """The 11 actor tensors of an SB3 RecurrentPPO state dict as contiguous f32 arrays, keyed by
     ha_weights field; ValueError for any architecture but 13 -> LSTM 128 x 1 -> 64 -> 64 -> 2."""
     return _net_from_state_dict(sd, "lstm_actor", "mlp_extractor.policy_net.", ACTOR_KEYS, "actor")
+
+
+def _f32(t):
+    a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def stack_weights_from_state_dict(sd):
+    """The actor of an SB3 RecurrentPPO state dict with lstm_hidden_size H in STACK_HIDDEN and n_lstm_layers
+    NL <= STACK_MAX_LAYERS, both read off the shapes: {"w_ih", "w_hh", "b_ih", "b_hh": lists of NL f32 arrays,
+    "w1" .. "b3" (and "log_std" where present): arrays}.  ValueError for another H or NL, an incomplete
+    layer, an obs other than 13 or an MLP other than 64-64 -> 2."""
+    stem = "lstm_actor.weight_ih_l"
+    layers = sorted(int(k[len(stem):]) for k in sd if k.startswith(stem) and k[len(stem):].isdigit())
+    nl = len(layers)
+    if layers != list(range(nl)) or not 1 <= nl <= STACK_MAX_LAYERS:
+        raise ValueError(f"lstm_actor has layers {layers}: n_lstm_layers 1 to {STACK_MAX_LAYERS} are built")
+    if "lstm_actor.weight_hh_l0" not in sd:
+        raise ValueError("state dict has no 'lstm_actor.weight_hh_l0'")
+    hid = int(np.shape(sd["lstm_actor.weight_hh_l0"])[-1])
+    if hid not in STACK_HIDDEN:
+        raise ValueError(f"lstm_hidden_size {hid}: {STACK_HIDDEN} are built")
+    extra = sorted(k for k in sd if k.startswith("mlp_extractor.policy_net.") and k.split(".")[2] not in ("0", "2"))
+    if extra:
+        raise ValueError(f"policy_net has layers beyond 64 -> 64: {extra}")
+    out = {f: [] for f in STACK_LSTM_FIELDS}
+    for l in range(nl):
+        n_in = hid if l else OBS_DIM
+        for name, field, shape in zip(STACK_LSTM_KEYS, STACK_LSTM_FIELDS,
+                                      ((4 * hid, n_in), (4 * hid, hid), (4 * hid,), (4 * hid,))):
+            key = f"lstm_actor.{name}_l{l}"
+            if key not in sd:
+                raise ValueError(f"state dict has no {key!r}: layer {l} is incomplete")
+            a = _f32(sd[key])
+            if a.shape != shape:
+                raise ValueError(f"{key} has shape {a.shape}, expected {shape} (obs {OBS_DIM}, lstm_hidden_size {hid})")
+            out[field].append(a)
+    for key, field, shape in _MLP_KEYS:
+        if key not in sd:
+            if field == "log_std":   # the deterministic action does not read it
+                continue
+            raise ValueError(f"state dict has no {key!r}")
+        a = _f32(sd[key])
+        shape = (MLP, hid) if field == "w1" else shape
+        if a.shape != shape:
+            raise ValueError(f"{key} has shape {a.shape}, expected {shape} (net_arch 64-64, 2 actions)")
+        out[field] = a
+    return out
 
 
 def policy_weights_from_state_dict(sd):
@@ -367,14 +432,22 @@ class RecurrentActor(_Recurrent):
         self._w.squash = SQUASHES[squash]
         self.squash = squash
 
+    def _state_shape(self, n):
+        return (n, HIDDEN)
+
+    @property
+    def num_envs(self):
+        """The env count the device state holds; 0 before reset_states."""
+        return 0 if self._sums is None else int(self._sums.shape[0])
+
     def reset_states(self, n_envs):
         """Zero h, c (and the episode sums) for n_envs envs."""
         import torch
         self._handle()
         n = int(n_envs)
-        if self.h is None or self.h.shape[0] != n:
-            self.h = torch.zeros((n, HIDDEN), dtype=torch.float32, device=self.device)
-            self.c = torch.zeros((n, HIDDEN), dtype=torch.float32, device=self.device)
+        if self.num_envs != n:
+            self.h = torch.zeros(self._state_shape(n), dtype=torch.float32, device=self.device)
+            self.c = torch.zeros(self._state_shape(n), dtype=torch.float32, device=self.device)
             self._sums = torch.zeros((n, EPISODE_SUMS.itemsize), dtype=torch.uint8, device=self.device)
         else:
             self.h.zero_()
@@ -387,7 +460,7 @@ class RecurrentActor(_Recurrent):
         updated in place.  Enqueued on the current stream, no host sync."""
         import torch
         h, n, episode_start = self._begin_step(obs, episode_start)
-        if self.h is None or self.h.shape[0] != n:
+        if self.num_envs != n:
             self.reset_states(n)
         if out is None:
             out = torch.empty((n, ACT_DIM), dtype=torch.float32, device=self.device)
@@ -418,15 +491,79 @@ class RecurrentActor(_Recurrent):
         """ha_host_step over NumPy: obs [n,13] f32, episode_start [n], h / c [n,128] f32 C-contiguous
         arrays updated IN PLACE; returns actions [n,2].  The device kernel's arithmetic on the CPU."""
         obs, es, n = self._host_inputs(obs, episode_start, ("h", "c"), (h, c))
+        return self._host_call("ha_host_step", obs, es, n, h, c, mean_out, obs_norm_out)
+
+    def _host_call(self, entry, obs, es, n, h, c, mean_out, obs_norm_out):
         act = np.empty((n, ACT_DIM), np.float32)
         for a, w in ((mean_out, ACT_DIM), (obs_norm_out, OBS_DIM)):
             if a is not None and not (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (n, w)):
                 raise ValueError("mean_out / obs_norm_out must be C-contiguous float32 of the step's shape")
-        st = self.lib.ha_host_step(ctypes.byref(self._w), n, obs.ctypes.data, es.ctypes.data, h.ctypes.data,
-                                   c.ctypes.data, act.ctypes.data, None if mean_out is None else mean_out.ctypes.data,
-                                   None if obs_norm_out is None else obs_norm_out.ctypes.data)
-        _check(self.lib, st, "ha_host_step")
+        st = getattr(self.lib, entry)(ctypes.byref(self._w), n, obs.ctypes.data, es.ctypes.data, h.ctypes.data,
+                                      c.ctypes.data, act.ctypes.data, None if mean_out is None else mean_out.ctypes.data,
+                                      None if obs_norm_out is None else obs_norm_out.ctypes.data)
+        _check(self.lib, st, entry)
         return act
+
+
+class StackedRecurrentActor(RecurrentActor):
+    """RecurrentActor for the wider and stacked LSTMs of sb3_contrib's policy_kwargs: lstm_hidden_size H in
+    STACK_HIDDEN (128, 256, 512), n_lstm_layers NL from 1 to 4, both read off the tensors' shapes; the
+    MLP stays 64-64 and the obs 13 (contract S1-S5 of include/hedge_actor.h, stack_step_kernel).
+
+    weights: a state dict (lstm_actor.*_l0 .. _l{NL-1}, mlp_extractor.policy_net.*, action_net.*) or
+    stack_weights_from_state_dict's fields.  The keywords are RecurrentActor's.  The states h, c are
+    [NL, n, H], SB3's lstm_states layout; step, accumulate and HedgingVecEnv.evaluate_actor are
+    RecurrentActor's.  At H = 128, NL = 1 every bit equals RecurrentActor's."""
+
+    _struct, _fields_of = HaStackWeights, staticmethod(stack_weights_from_state_dict)
+    _create = "ha_stack_create"
+
+    def _set_tensors(self, weights):
+        if any("." in k for k in weights):
+            weights = self._fields_of(weights)
+        lstm = {f: [np.ascontiguousarray(a, dtype=np.float32) for a in weights[f]] for f in STACK_LSTM_FIELDS}
+        nl = len(lstm["w_hh"])
+        if not 1 <= nl <= STACK_MAX_LAYERS or any(len(v) != nl for v in lstm.values()):
+            raise ValueError(f"w_ih, w_hh, b_ih, b_hh are lists of one array per layer, 1 to {STACK_MAX_LAYERS} layers")
+        hid = lstm["w_hh"][0].shape[-1]
+        if hid not in STACK_HIDDEN:
+            raise ValueError(f"lstm_hidden_size {hid}: {STACK_HIDDEN} are built")
+        for l in range(nl):
+            shapes = ((4 * hid, hid if l else OBS_DIM), (4 * hid, hid), (4 * hid,), (4 * hid,))
+            for f, shape in zip(STACK_LSTM_FIELDS, shapes):
+                if lstm[f][l].shape != shape:
+                    raise ValueError(f"{f}[{l}] has shape {lstm[f][l].shape}, expected {shape}")
+        arrays = dict(lstm)
+        for _, f, shape in _MLP_KEYS:
+            if f == "log_std" and weights.get(f) is None:
+                continue
+            a = np.ascontiguousarray(weights[f], dtype=np.float32)
+            shape = (MLP, hid) if f == "w1" else shape
+            if a.shape != shape:
+                raise ValueError(f"{f} has shape {a.shape}, expected {shape}")
+            arrays[f] = a
+        self._arrays.update(arrays)   # the struct points into these
+        w = self._w
+        w.hidden, w.n_lstm_layers = hid, nl
+        for f in STACK_LSTM_FIELDS:
+            setattr(w, f, (_F * STACK_MAX_LAYERS)(*(a.ctypes.data_as(_F) for a in lstm[f])))
+        for _, f, _ in _MLP_KEYS:
+            if f in arrays:
+                setattr(w, f, arrays[f].ctypes.data_as(_F))
+        self.hidden, self.n_lstm_layers = hid, nl
+
+    def _state_shape(self, n):
+        return (self.n_lstm_layers, n, self.hidden)
+
+    def host_step(self, obs, episode_start, h, c, mean_out=None, obs_norm_out=None):
+        """ha_host_stack_step over NumPy: as RecurrentActor.host_step with h / c [NL, n, H] f32 C-contiguous
+        arrays updated IN PLACE."""
+        obs, es, n = self._host_inputs(obs, episode_start, (), ())
+        for name, a in (("h", h), ("c", c)):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous
+                    and a.shape == self._state_shape(n)):
+                raise ValueError(f"{name} must be a C-contiguous float32 {list(self._state_shape(n))} array")
+        return self._host_call("ha_host_stack_step", obs, es, n, h, c, mean_out, obs_norm_out)
 
 
 STATE_NAMES = ("h_pi", "c_pi", "h_vf", "c_vf")

@@ -27,8 +27,9 @@
 // one thread per env over [K][n] arrays.  lstm_seq_fwd_kernel / lstm_seq_bwd_kernel (the PPO update's
 // LSTM over a stored sequence, forward and backward) and lstm_wgrad_kernel / lstm_wgrad_reduce_kernel
 // (its weight gradients), policy_pack_kernel (ha_policy_refresh), opt_norm_kernel / opt_adam_kernel
-// (ha_adam_step), the four loss_*_kernel (ha_ppo_loss) and the four heads_*_kernel (ha_ppo_heads_forward /
-// _backward) are described where they stand.
+// (ha_adam_step), the four loss_*_kernel (ha_ppo_loss), the four heads_*_kernel (ha_ppo_heads_forward /
+// _backward) and stack_step_kernel (ha_step for hidden 128 / 256 / 512 and one to four LSTM layers) are
+// described where they stand.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -318,6 +319,193 @@ __global__ __launch_bounds__(256) void accumulate_kernel(int64_t n, int64_t goff
     sums[e] = s;
 }
 
+// ---------------------------------------------------------------- stacked and wide LSTMs (contract S1-S5)
+// stack_step_kernel<H> (ha_step on a handle of ha_stack_create): H = 128, 256 or 512 hidden units, one
+// to four layers.  A workgroup of H / 32 waves (4, 8, 16) owns a tile of 32 envs and walks the layers;
+// wave w owns units 32 w .. 32 w + 31 of EVERY layer and keeps their four gate accumulators, so the cell
+// update stays in registers as in actor_kernel.
+//   LDS      op[16 + 2 H][33]: rows 3 .. 15 hold x, rows 16 .. 16 + H - 1 the input half I, the next H
+//            rows the recurrent half R.  Layer 0 reads the B operand [x | h[0] | 0] from row 3 on (h[0]
+//            staged into I, the padding term a zero operand in the last k-step), layer l >= 1 reads
+//            [h'[l-1] | h[l]] = [I | R] from row 16 on.  135 KB of halves at H = 512: one workgroup a CU.
+//   layer    the whole K (14 + H, then 2 H) runs through one accumulator per gate from b_ih + b_hh: the
+//            chain of S3.  Barrier; h'[l] from registers overwrites I, h[l+1] (zeroed at an episode start)
+//            is staged from global into R; barrier.  c is read and written as float4 from registers.
+//   weights  float4 {i, f, g, o}[layer][wave][k-step][lane], the layers back to back: one 16-byte load a
+//            lane feeds four independent MFMAs.  29 MB at 512 x 4, streamed from L2 / Infinity Cache.
+//   MLP      waves 0, 1 run mlp_slice<H> on I, a1 / a2 live in R; the head is head_chain.
+// 16 waves a workgroup are 4 a SIMD: at most 128 registers a lane at H = 512.
+constexpr int kStackXrow = 3;    // x ends where I begins
+constexpr int kStackIrow = 16;
+constexpr int stack_steps(int hid, int layer) { return layer ? hid : (kObs + hid + 1) / 2; }   // k-steps of a layer
+
+// the blob of a stacked actor, in floats; every section a multiple of 4 floats (16-byte aligned):
+//   0      float4 {i, f, g, o}[NL][H / 32][steps][64], the gate fragments
+//   o_bg   [NL][4 H] b_ih + b_hh
+//   o_w1   w1p [2][H / 2][64], b1 [64], w2p [2][32][64], b2 [64], w3 [2][64], b3 [2] (+ 2), as pack_net's
+//   o_st   the statistics, [3][13] doubles
+struct StackLayout {
+    size_t o_bg, o_w1, o_b1, o_w2, o_b2, o_w3, o_b3, o_st, total;
+    HE_HD StackLayout(int hid, int nl) {
+        o_bg = (size_t)(hid / 32) * 64 * 4 * (stack_steps(hid, 0) + (size_t)(nl - 1) * stack_steps(hid, 1));
+        o_w1 = o_bg + (size_t)nl * 4 * hid, o_b1 = o_w1 + (size_t)kMlp * hid, o_w2 = o_b1 + kMlp;
+        o_b2 = o_w2 + (size_t)kMlp * kMlp, o_w3 = o_b2 + kMlp, o_b3 = o_w3 + kAct * kMlp, o_st = o_b3 + 4;
+        total = o_st + 2 * 3 * kObs;
+    }
+};
+
+struct StackParams {
+    int64_t n;
+    const float* obs;
+    const uint8_t* start;
+    float* h;             // [NL][n][H]
+    float* c;
+    float* actions;
+    float* mean_out;
+    float* obs_norm_out;
+    const float* blob;    // the packed tensors, sections as StackLayout places them
+    const double* stats;  // as Params
+    double clip;
+    int32_t has_clip, relu, tanh_squash, n_layers;
+};
+
+// h[l] of the tile into dst[u][env]: zero where an episode starts and past n
+template <int H>
+__device__ __forceinline__ void stack_stage(float (*dst)[kLd], const float* __restrict__ hl, int64_t n, int64_t e0,
+                                            const uint8_t* __restrict__ start, int tid) {
+    for (int idx = tid; idx < kTile * H; idx += 2 * H) {
+        const int el = idx / H, u = idx & (H - 1);
+        const int64_t e = e0 + el;
+        float v = 0.0f;
+        if (e < n && !start[e]) v = hl[e * H + u];
+        dst[u][el] = v;
+    }
+}
+
+template <int H>
+__global__ __launch_bounds__(2 * H) void stack_step_kernel(const StackParams p) {
+    static_assert(H == 128 || H == 256 || H == 512, "whole waves of 32 units, LDS within 160 KB");
+    constexpr int kT = 2 * H;
+    __shared__ float op[kStackIrow + 2 * H][kLd];
+    float (*const I)[kLd] = op + kStackIrow;
+    float (*const R)[kLd] = I + H;
+    const int tid = threadIdx.x;
+    const int64_t e0 = (int64_t)blockIdx.x * kTile;
+    // ---- stage x and h[0]; envs past n are zero columns
+    for (int idx = tid; idx < kTile * kObs; idx += kT) {
+        const int el = idx / kObs, k = idx - el * kObs;
+        const int64_t e = e0 + el;
+        float v = 0.0f;
+        if (e < p.n) {
+            v = p.obs[e * kObs + k];
+            if (p.stats) v = norm_obs(v, p.stats[k], p.stats[kObs + k], p.stats[2 * kObs + k], p.has_clip != 0, p.clip);
+            if (p.obs_norm_out) p.obs_norm_out[e * kObs + k] = v;
+        }
+        op[kStackXrow + k][el] = v;
+    }
+    stack_stage<H>(I, p.h, p.n, e0, p.start, tid);
+    __syncthreads();
+
+    // Every phase of a layer derives its lane indices afresh from an opaque copy of tid: what the staging,
+    // the cell update and the stores index by (addresses, episode flags) would otherwise be hoisted out of
+    // the layer loop and held beside the 64 accumulators, past the 128 registers a lane has at H = 512.
+    size_t wofs = 0;   // the layer's fragments, in float4
+    for (int l = 0; l < p.n_layers; ++l) {
+        int t = tid;
+        asm volatile("" : "+v"(t));
+        // ---- gates: [x | h[0] | 0] from row 3 for layer 0, [I | R] from row 16 above it
+        const int row0 = l ? kStackIrow : kStackXrow;
+        const int steps = stack_steps(H, l);
+        const int full = l ? steps : steps - 1;   // layer 0's last k-step pairs h[0][H-1] with the padding term
+        f32x16 acc[4];
+        {
+            const int wave = t >> 6, lane = t & 63, col = lane & 31, hi = lane >> 5;
+            const float* bg = p.blob + StackLayout(H, p.n_layers).o_bg + (size_t)l * 4 * H + wave * 32 + 4 * hi;
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float4 b = *(const float4*)(bg + g * H + 8 * q);
+                    acc[g][4 * q + 0] = b.x; acc[g][4 * q + 1] = b.y; acc[g][4 * q + 2] = b.z; acc[g][4 * q + 3] = b.w;
+                }
+            const float4* wp = (const float4*)p.blob + wofs + (size_t)wave * steps * 64 + lane;
+            const float* bp = &op[row0 + hi][col];
+#pragma unroll 4
+            for (int s = 0; s < full; ++s) {
+                const float4 w = wp[s * 64];
+                const float b = bp[2 * s * kLd];
+                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, b, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, b, acc[1], 0, 0, 0);
+                acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, b, acc[2], 0, 0, 0);
+                acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, b, acc[3], 0, 0, 0);
+            }
+            if (!l) {
+                const float4 w = wp[full * 64];
+                const float b = hi ? 0.0f : bp[2 * full * kLd];
+                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, b, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, b, acc[1], 0, 0, 0);
+                acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, b, acc[2], 0, 0, 0);
+                acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, b, acc[3], 0, 0, 0);
+            }
+            wofs += (size_t)(H / 32) * steps * 64;
+        }
+        // ---- cell update in registers; h' stays in acc[0] until I may be overwritten
+        float* hl = p.h + (size_t)l * p.n * H;
+        float* cl = p.c + (size_t)l * p.n * H;
+        asm volatile("" : "+v"(t));
+        {
+            const int64_t e = e0 + (t & 31);
+            const bool valid = e < p.n;
+            const bool fresh = valid && p.start[e] != 0;
+            const size_t at = (size_t)e * H + (t >> 6) * 32 + 4 * ((t >> 5) & 1);   // + 8 q: four units of (unit group, half)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                float4 cv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (valid && !fresh) cv = *(const float4*)(cl + at + 8 * q);
+                float cc[4] = {cv.x, cv.y, cv.z, cv.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int r = 4 * q + j;
+                    acc[0][r] = cell_update(acc[0][r], acc[1][r], acc[2][r], acc[3][r], &cc[j]);
+                }
+                if (valid) {
+                    *(float4*)(cl + at + 8 * q) = make_float4(cc[0], cc[1], cc[2], cc[3]);
+                    *(float4*)(hl + at + 8 * q) =
+                        make_float4(acc[0][4 * q], acc[0][4 * q + 1], acc[0][4 * q + 2], acc[0][4 * q + 3]);
+                }
+            }
+        }
+        __syncthreads();   // every wave has read layer l's operand
+        asm volatile("" : "+v"(t));
+        {
+            float* ip = &I[(t >> 6) * 32 + 4 * ((t >> 5) & 1)][t & 31];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) ip[((r & 3) + 8 * (r >> 2)) * kLd] = acc[0][r];
+            if (l + 1 < p.n_layers) stack_stage<H>(R, hl + (size_t)p.n * H, p.n, e0, p.start, t);
+        }
+        __syncthreads();
+    }
+    const int wave = tid >> 6, lane = tid & 63;
+
+    // ---- MLP on I = h'[NL-1]; a1, a2 reuse the recurrent half
+    float (*const a1)[kLd] = R;
+    float (*const a2)[kLd] = R + kMlp;
+    const StackLayout L(H, p.n_layers);
+    if (wave < 2) mlp_slice<H>(p.blob + L.o_w1, p.blob + L.o_b1, I, a1, wave, lane, p.relu != 0);
+    __syncthreads();
+    if (wave < 2) mlp_slice<kMlp>(p.blob + L.o_w2, p.blob + L.o_b2, a1, a2, wave, lane, p.relu != 0);
+    __syncthreads();
+    if (tid < kTile * kAct) {
+        const int el = tid >> 1, j = tid & 1;
+        const int64_t eh = e0 + el;
+        const float m = head_chain(p.blob + L.o_w3 + j * kMlp, p.blob[L.o_b3 + j], a2, el);
+        if (eh < p.n) {
+            if (p.mean_out) p.mean_out[eh * kAct + j] = m;
+            p.actions[eh * kAct + j] = squash_action(m, p.tanh_squash != 0);
+        }
+    }
+}
+
 thread_local char g_err[256] = "";
 
 }  // namespace
@@ -326,6 +514,8 @@ struct ha_actor {
     char err[256];
     void* blob;   // one device allocation holding every packed tensor
     Params p;     // the constant part of the kernel's arguments
+    StackParams sp;     // the same of a handle of ha_stack_create
+    int stack_hidden;   // its H; 0: a handle of ha_create
 };
 
 struct ha_policy {
@@ -537,11 +727,12 @@ struct HostNorm {
     }
 };
 
-// THE 64-64 MLP of the contract on the host (step 5, H1) for one env or row: the two layers into a1, a2
-void host_mlp(const HeadsNetW& w, const float* h, bool relu, float* a1, float* a2) {
+// THE 64-64 MLP of the contract on the host (step 5, H1, S4) for one env or row: the two layers into a1, a2;
+// hid: the width of h
+void host_mlp(const HeadsNetW& w, const float* h, bool relu, float* a1, float* a2, int hid = kHid) {
     for (int j = 0; j < kMlp; ++j) {
         float acc = w.b1[j];
-        for (int k = 0; k < kHid; ++k) acc = fmaf(w.w1[j * kHid + k], h[k], acc);
+        for (int k = 0; k < hid; ++k) acc = fmaf(w.w1[j * hid + k], h[k], acc);
         a1[j] = mlp_act(acc, relu);
     }
     for (int j = 0; j < kMlp; ++j) {
@@ -575,6 +766,148 @@ void host_net_env(const HostNet& w, const float* x, bool fresh, float* h, float*
         memcpy(c, cn, sizeof cn);
     }
     host_mlp(w.heads(), hn, relu, a1, a2);
+}
+
+// ---------------------------------------------------------------- stacked and wide LSTMs: checks, packing, host
+ha_status check_stack_weights(const ha_stack_weights* w) {
+    char m[200];
+    if (!w) return fail_to(nullptr, HE_EINVAL, "weights is NULL");
+    if (w->abi_version != HA_ABI_VERSION) return fail_to(nullptr, HE_EINVAL, "ha_stack_weights.abi_version mismatch");
+    if (w->hidden != 128 && w->hidden != 256 && w->hidden != 512) {
+        snprintf(m, sizeof m, "hidden = %d: the stacked actor is built for 128, 256 and 512", w->hidden);
+        return fail_to(nullptr, HE_ESHAPE, m);
+    }
+    if (w->n_lstm_layers < 1 || w->n_lstm_layers > HA_STACK_MAX_LAYERS) {
+        snprintf(m, sizeof m, "n_lstm_layers = %d: the stacked actor is built for 1 to %d", w->n_lstm_layers,
+                 HA_STACK_MAX_LAYERS);
+        return fail_to(nullptr, HE_ESHAPE, m);
+    }
+    const struct { const char* name; int got, want; } dims[] = {
+        {"obs_dim", w->obs_dim, kObs}, {"mlp_width", w->mlp_width, kMlp}, {"act_dim", w->act_dim, kAct}};
+    for (const auto& d : dims)
+        if (d.got != d.want) {
+            snprintf(m, sizeof m, "%s = %d: only %d is built", d.name, d.got, d.want);
+            return fail_to(nullptr, HE_ESHAPE, m);
+        }
+    if (w->activation != HA_ACT_TANH && w->activation != HA_ACT_RELU) return fail_to(nullptr, HE_EINVAL, "unknown activation");
+    if (w->squash != HA_SQUASH_CLIP && w->squash != HA_SQUASH_TANH) return fail_to(nullptr, HE_EINVAL, "unknown squash");
+    bool complete = w->w1 && w->b1 && w->w2 && w->b2 && w->w3 && w->b3;
+    for (int l = 0; l < w->n_lstm_layers; ++l) complete = complete && w->w_ih[l] && w->w_hh[l] && w->b_ih[l] && w->b_hh[l];
+    if (!complete) return fail_to(nullptr, HE_EINVAL, "an actor tensor is NULL");
+    if ((w->obs_mean == nullptr) != (w->obs_var == nullptr))
+        return fail_to(nullptr, HE_EINVAL, "obs_mean and obs_var come together");
+    return HE_OK;
+}
+
+HeadsNetW stack_heads(const ha_stack_weights* w) { return {w->w1, w->b1, w->w2, w->b2, w->w3, w->b3, kAct}; }
+
+void pack_stack(const ha_stack_weights* w, const StackLayout& L, float* dst) {
+    const int hid = w->hidden, nl = w->n_lstm_layers;
+    float* f = dst;
+    for (int l = 0; l < nl; ++l) {
+        const int n_in = l ? hid : kObs, steps = stack_steps(hid, l);
+        for (int ug = 0; ug < hid / 32; ++ug)
+            for (int s = 0; s < steps; ++s)
+                for (int ln = 0; ln < 64; ++ln)
+                    for (int g = 0; g < 4; ++g) {
+                        const size_t j = (size_t)g * hid + ug * 32 + (ln & 31);
+                        const int k = 2 * s + (ln >> 5);
+                        *f++ = k < n_in ? w->w_ih[l][j * n_in + k] : (k < n_in + hid ? w->w_hh[l][j * hid + (k - n_in)] : 0.0f);
+                    }
+        for (int j = 0; j < 4 * hid; ++j) dst[L.o_bg + (size_t)l * 4 * hid + j] = w->b_ih[l][j] + w->b_hh[l][j];
+    }
+    for (int rt = 0; rt < 2; ++rt)
+        for (int ln = 0; ln < 64; ++ln) {
+            for (int s = 0; s < hid / 2; ++s)
+                dst[L.o_w1 + ((size_t)rt * (hid / 2) + s) * 64 + ln] = w->w1[(rt * 32 + (ln & 31)) * hid + 2 * s + (ln >> 5)];
+            for (int s = 0; s < kMlp / 2; ++s)
+                dst[L.o_w2 + ((size_t)rt * (kMlp / 2) + s) * 64 + ln] = w->w2[(rt * 32 + (ln & 31)) * kMlp + 2 * s + (ln >> 5)];
+        }
+    memcpy(dst + L.o_b1, w->b1, kMlp * sizeof(float));
+    memcpy(dst + L.o_b2, w->b2, kMlp * sizeof(float));
+    memcpy(dst + L.o_w3, w->w3, (size_t)kAct * kMlp * sizeof(float));
+    memcpy(dst + L.o_b3, w->b3, kAct * sizeof(float));
+    if (w->obs_mean) pack_stats(w->obs_mean, w->obs_var, w->epsilon, dst + L.o_st);
+}
+
+// nk terms of S3's chains for a block of kTile envs at once: acc[e] = fmaf(w[k], z[k][e], acc[e]), k in
+// order.  Every env's chain is the scalar one; the envs run side by side, so the loop vectorises over
+// them.  The x86-64 copy with the FMA unit named is the same bits sooner (as wgrad_row's).
+#define HA_STACK_ROW_BODY                                                          \
+    for (int k = 0; k < nk; ++k) {                                                 \
+        const float a = w[k];                                                      \
+        const float* zk = z + (size_t)k * kTile;                                   \
+        for (int e = 0; e < kTile; ++e) acc[e] = __builtin_fmaf(a, zk[e], acc[e]); \
+    }
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+#define HA_STACK_FMA_COPY 1
+__attribute__((target("avx2,fma"))) void stack_row_fma(const float* __restrict__ w, const float* __restrict__ z, int nk,
+                                                       float* __restrict__ acc) {
+    HA_STACK_ROW_BODY
+}
+#endif
+void stack_row(const float* __restrict__ w, const float* __restrict__ z, int nk, float* __restrict__ acc) {
+#ifdef HA_STACK_FMA_COPY
+    static const bool fma_unit = __builtin_cpu_supports("avx2") && __builtin_cpu_supports("fma");
+    if (fma_unit) return stack_row_fma(w, z, nk, acc);
+#endif
+    HA_STACK_ROW_BODY
+}
+#undef HA_STACK_ROW_BODY
+
+// Contract S1-S4 on the host for the nb <= kTile envs from e0 on
+void host_stack_block(const ha_stack_weights* w, const HostNorm& norm, int64_t n, int64_t e0, int nb, const float* obs,
+                      const uint8_t* start, float* h, float* c, float* actions, float* mean_out, float* obs_norm_out) {
+    const int hid = w->hidden, nl = w->n_lstm_layers;
+    const bool relu = w->activation == HA_ACT_RELU, tsq = w->squash == HA_SQUASH_TANH;
+    // operands as [k][env]; envs past nb are zero columns
+    std::vector<float> in((size_t)hid * kTile, 0.0f), out((size_t)hid * kTile, 0.0f), rec((size_t)hid * kTile, 0.0f);
+    for (int el = 0; el < nb; ++el) {
+        float x[kObs];
+        norm.env(obs, e0 + el, x, obs_norm_out);
+        for (int k = 0; k < kObs; ++k) in[(size_t)k * kTile + el] = x[k];
+    }
+    for (int l = 0; l < nl; ++l) {
+        const int n_in = l ? hid : kObs;
+        float* hl = h + (size_t)l * n * hid;
+        float* cl = c + (size_t)l * n * hid;
+        for (int el = 0; el < nb; ++el)
+            for (int u = 0; u < hid; ++u) rec[(size_t)u * kTile + el] = start[e0 + el] ? 0.0f : hl[(e0 + el) * hid + u];
+        for (int u = 0; u < hid; ++u) {
+            float pre[4][kTile];
+            for (int g = 0; g < 4; ++g) {
+                const size_t j = (size_t)g * hid + u;
+                const float b = w->b_ih[l][j] + w->b_hh[l][j];
+                for (int el = 0; el < kTile; ++el) pre[g][el] = b;
+                stack_row(w->w_ih[l] + j * n_in, in.data(), n_in, pre[g]);
+                stack_row(w->w_hh[l] + j * hid, rec.data(), hid, pre[g]);
+                if ((n_in + hid) & 1)   // the zero-weight padding term
+                    for (int el = 0; el < kTile; ++el) pre[g][el] = fmaf(0.0f, 0.0f, pre[g][el]);
+            }
+            for (int el = 0; el < nb; ++el) {
+                const int64_t e = e0 + el;
+                float cv = start[e] ? 0.0f : cl[e * hid + u];
+                const float hn = cell_update(pre[0][el], pre[1][el], pre[2][el], pre[3][el], &cv);
+                cl[e * hid + u] = cv;
+                hl[e * hid + u] = hn;   // rec holds what this layer reads
+                out[(size_t)u * kTile + el] = hn;
+            }
+        }
+        in.swap(out);   // h'[l] feeds the layer above
+    }
+    const HeadsNetW head = stack_heads(w);
+    std::vector<float> hv(hid);
+    for (int el = 0; el < nb; ++el) {
+        const int64_t e = e0 + el;
+        float a1[kMlp], a2[kMlp];
+        for (int u = 0; u < hid; ++u) hv[u] = in[(size_t)u * kTile + el];
+        host_mlp(head, hv.data(), relu, a1, a2, hid);
+        for (int j = 0; j < kAct; ++j) {
+            const float m = host_head(head, j, a2);
+            if (mean_out) mean_out[e * kAct + j] = m;
+            actions[e * kAct + j] = squash_action(m, tsq);
+        }
+    }
 }
 
 // the blob of a policy: [actor | critic | log_std, std | statistics]
@@ -2118,6 +2451,22 @@ ha_status ha_step(ha_actor* actor, int64_t n, const float* obs, const uint8_t* e
     if (n < 1 || n > ((int64_t)1 << 30)) return fail(actor, HE_EINVAL, "n must be in [1, 2^30]");
     if (!obs || !episode_start || !h || !c || !actions) return fail(actor, HE_EINVAL, "a required buffer is NULL");
     if ((((uintptr_t)h) | ((uintptr_t)c)) & 15u) return fail(actor, HE_EINVAL, "h and c must be 16-byte aligned");
+    if (actor->stack_hidden) {   // a handle of ha_stack_create: h, c are [NL][n][H]
+        StackParams sp = actor->sp;
+        sp.n = n;
+        sp.obs = obs;
+        sp.start = episode_start;
+        sp.h = h;
+        sp.c = c;
+        sp.actions = actions;
+        sp.mean_out = mean_out;
+        sp.obs_norm_out = obs_norm_out;
+        const dim3 tiles((unsigned)((n + kTile - 1) / kTile)), block(2 * actor->stack_hidden);
+        const char* name = "stack_step_kernel";
+        if (actor->stack_hidden == 128) return launch(actor->err, stack_step_kernel<128>, tiles, block, stream, name, sp);
+        if (actor->stack_hidden == 256) return launch(actor->err, stack_step_kernel<256>, tiles, block, stream, name, sp);
+        return launch(actor->err, stack_step_kernel<512>, tiles, block, stream, name, sp);
+    }
     Params p = actor->p;
     p.n = n;
     p.obs = obs;
@@ -2170,6 +2519,42 @@ ha_status ha_host_step(const ha_weights* w, int64_t n, const float* obs, const u
             actions[e * kAct + j] = squash_action(m, tsq);
         }
     }
+    return HE_OK;
+}
+
+ha_status ha_stack_create(const ha_stack_weights* w, ha_actor** out) {
+    if (!out) return fail_to(nullptr, HE_EINVAL, "out is NULL");
+    *out = nullptr;
+    ha_status st = check_stack_weights(w);
+    if (st != HE_OK) return st;
+    const StackLayout L(w->hidden, w->n_lstm_layers);
+    std::vector<float> hbuf(L.total, 0.0f);
+    pack_stack(w, L, hbuf.data());
+    st = create_handle(hbuf, out);
+    if (st != HE_OK) return st;
+    const float* d = (const float*)(*out)->blob;
+    StackParams& p = (*out)->sp;
+    memset(&p, 0, sizeof p);
+    p.blob = d;
+    p.stats = w->obs_mean ? (const double*)(d + L.o_st) : nullptr;
+    p.clip = w->clip_obs;
+    p.has_clip = w->has_clip;
+    p.relu = w->activation == HA_ACT_RELU;
+    p.tanh_squash = w->squash == HA_SQUASH_TANH;
+    p.n_layers = w->n_lstm_layers;
+    (*out)->stack_hidden = w->hidden;
+    return HE_OK;
+}
+
+ha_status ha_host_stack_step(const ha_stack_weights* w, int64_t n, const float* obs, const uint8_t* episode_start,
+                             float* h, float* c, float* actions, float* mean_out, float* obs_norm_out) {
+    const ha_status st = check_stack_weights(w);
+    if (st != HE_OK) return st;
+    if (n < 1 || !obs || !episode_start || !h || !c || !actions) return fail_to(nullptr, HE_EINVAL, "bad argument");
+    const HostNorm norm(w->obs_mean, w->obs_var, w->epsilon, w->has_clip != 0, w->clip_obs);
+    for (int64_t e0 = 0; e0 < n; e0 += kTile)
+        host_stack_block(w, norm, n, e0, (int)(n - e0 < kTile ? n - e0 : kTile), obs, episode_start, h, c, actions,
+                         mean_out, obs_norm_out);
     return HE_OK;
 }
 

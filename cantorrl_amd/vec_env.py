@@ -576,7 +576,7 @@ class HedgingVecEnv:
 
     def rollout_actor(self, actor, k_steps, actions_out=None, obs=None, reward=None, terminated=None,
                       records=None, record_count=None):
-        """k_steps closed-loop steps driven by a RecurrentActor (agent.py): per step ha_step on the
+        """k_steps closed-loop steps driven by a RecurrentActor or StackedRecurrentActor (agent.py): per step ha_step on the
         current obs and the last step's `terminated` (ones after a reset), he_step, ha_accumulate,
         all enqueued on the current stream with no host sync.  actions_out [K,N,2], obs [K,N,13],
         reward [K,N], terminated [K,N] are filled as `rollout` fills them (each may be None).
@@ -591,7 +591,7 @@ class HedgingVecEnv:
             if t is not None and (tuple(t.shape) != shape or not t.is_contiguous()):
                 raise ValueError(f"{name} must be a contiguous tensor of shape {shape}")
         st = self._actor_start
-        if st is None or st[0] is not actor or actor.h is None or actor.h.shape[0] != n:
+        if st is None or st[0] is not actor or actor.num_envs != n:
             # a new pairing (or the env was reset): every env begins an episode
             actor.reset_states(n)
             start = torch.ones(n, dtype=torch.uint8, device=self.device)

@@ -32,6 +32,22 @@
  *      mean = chain(action_net).
  *   6. action = clip(mean, -1, 1) (HA_SQUASH_CLIP) or clip(f32(tanh_f64(mean)), -1, 1).
  *
+ * Stacked and wide LSTMs (ha_stack_create, ha_host_stack_step: torch's stacked nn.LSTM as sb3_contrib's
+ * lstm_hidden_size / n_lstm_layers build it).  H in {128, 256, 512}, NL in {1, 2, 3, 4}; the states h, c
+ * are [NL][n][H], SB3's lstm_states layout (n_layers, n_envs, hidden).  Per env e:
+ *   S1. episode_start[e] != 0: h[l][e][:] = c[l][e][:] = 0 for every layer l.
+ *   S2. x as step 2 (the statistics, f64, rounded once).
+ *   S3. layer l = 0 .. NL-1, gates i, f, g, o in torch's row order: in_0 = x (13 terms), in_l = h'[l-1]
+ *       for l >= 1 (H terms: this step's new output of the layer below, as torch's stacked nn.LSTM
+ *       feeds it).  pre[j] is the k-ordered f32 fmaf chain from b_ih_l[j] + b_hh_l[j] (one f32 add)
+ *       over W_ih_l[j,k] in_l[k], then over W_hh_l[j,k] h[l][k], k = 0 .. H-1, then one zero-weight
+ *       padding term where the term count is odd (layer 0 only).  The cell update is step 4, giving
+ *       c'[l] and h'[l].
+ *   S4. step 5 with W1 of shape [64][H] on h'[NL-1], then W2 [64][64], action_net [2][64], and step 6.
+ *   S5. at H = 128, NL = 1 every bit equals ha_step / ha_host_step for the same tensors: S1-S4 reduce
+ *       to steps 1-6 there.
+ *   Nothing in S1-S5 depends on the grid.
+ *
  * Rollout collection (ha_policy_step, ha_gae: what sb3_contrib RecurrentPPO.collect_rollouts
  * computes per step, and SB3 2.6.0 RolloutBuffer.compute_returns_and_advantage after it;
  * restated, SB3 is not a dependency).  Per env e:
@@ -271,6 +287,50 @@ ha_status ha_accumulate(ha_actor* actor, int64_t n, int64_t env_id_offset, const
 /* ha_step's arithmetic on the host, HOST pointers, straight from the unpacked tensors. */
 ha_status ha_host_step(const ha_weights* w, int64_t n, const float* obs, const uint8_t* episode_start, float* h,
                        float* c, float* actions, float* mean_out, float* obs_norm_out);
+
+/* ---- stacked and wide LSTMs (S1-S5): hidden 128, 256 or 512, one to four layers ---- */
+#define HA_STACK_MAX_LAYERS 4
+
+/* ha_weights with one LSTM tensor per layer: HOST pointers, torch layout.  Entries at or past
+ * n_lstm_layers are ignored. */
+typedef struct ha_stack_weights {
+    int32_t abi_version;   /* HA_ABI_VERSION */
+    int32_t obs_dim;       /* 13 */
+    int32_t hidden;        /* H: 128, 256 or 512 */
+    int32_t n_lstm_layers; /* NL: 1 .. 4 */
+    int32_t mlp_width;     /* 64 */
+    int32_t act_dim;       /* 2 */
+    int32_t activation;    /* ha_activation */
+    int32_t squash;        /* ha_squash */
+    int32_t has_clip;
+    int32_t reserved;
+    double clip_obs;
+    double epsilon;
+    const float* w_ih[HA_STACK_MAX_LAYERS]; /* lstm_actor.weight_ih_l{l}: [4H][13] for l = 0, else [4H][H] */
+    const float* w_hh[HA_STACK_MAX_LAYERS]; /* lstm_actor.weight_hh_l{l} [4H][H] */
+    const float* b_ih[HA_STACK_MAX_LAYERS]; /* lstm_actor.bias_ih_l{l}   [4H]    */
+    const float* b_hh[HA_STACK_MAX_LAYERS]; /* lstm_actor.bias_hh_l{l}   [4H]    */
+    const float* w1;       /* mlp_extractor.policy_net.0.weight [64][H] */
+    const float* b1;
+    const float* w2;       /* [64][64] */
+    const float* b2;
+    const float* w3;       /* action_net.weight [2][64] */
+    const float* b3;
+    const float* log_std;  /* not used, may be NULL */
+    const double* obs_mean; /* [13] or NULL: both NULL = no normalisation */
+    const double* obs_var;
+} ha_stack_weights;
+
+/* As ha_create, for any H in {128, 256, 512} and NL in 1 .. 4: another hidden / n_lstm_layers, or anything
+ * but 13 / 64 / 2 for the rest, is HE_ESHAPE with a message naming the field.  Every tensor is packed
+ * once, in stack_step_kernel's fragment order, into one device allocation.  The handle is an ha_actor:
+ * ha_step on it takes h, c as [NL][n][H] (16-byte aligned), updates them in place and launches
+ * stack_step_kernel; ha_accumulate, ha_destroy and ha_last_error work on it unchanged. */
+ha_status ha_stack_create(const ha_stack_weights* w, ha_actor** out);
+
+/* S1-S5 on the host, HOST pointers, straight from the unpacked tensors; h, c [NL][n][H] in place. */
+ha_status ha_host_stack_step(const ha_stack_weights* w, int64_t n, const float* obs, const uint8_t* episode_start,
+                             float* h, float* c, float* actions, float* mean_out, float* obs_norm_out);
 
 /* ---- rollout collection: actor + critic + sampling in one launch, and GAE ---- */
 #define HA_POLICY_ABI_VERSION 1

@@ -100,14 +100,75 @@ def measure(n, reps):
                 speedup_vs_torch=round(t_torch / t_kernel, 2), reps=reps, device=torch.cuda.get_device_name(0))
 
 
+class TorchStack(torch.nn.Module):
+    """What a user has without stack_step_kernel: nn.LSTM (hidden x layers) stepped one time step at a
+    time, the state masked at starts, two Linear + tanh, the action head, clip; f32."""
+
+    def __init__(self, hidden, layers, mean, var):
+        super().__init__()
+        self.lstm = torch.nn.LSTM(13, hidden, layers)
+        self.l1, self.l2, self.head = torch.nn.Linear(hidden, 64), torch.nn.Linear(64, 64), torch.nn.Linear(64, 2)
+        self.register_buffer("mean", torch.from_numpy(mean).float())
+        self.register_buffer("inv_sd", torch.from_numpy(1.0 / np.sqrt(var + 1e-8)).float())
+
+    @torch.no_grad()
+    def forward(self, obs, start, h, c):
+        x = torch.clamp((obs - self.mean) * self.inv_sd, -10.0, 10.0)
+        keep = (1 - start).to(torch.float32)[None, :, None]
+        y, (h, c) = self.lstm(x[None], (h * keep, c * keep))
+        a = torch.tanh(self.l2(torch.tanh(self.l1(y[0]))))
+        return torch.clamp(self.head(a), -1.0, 1.0), h, c
+
+    def state_dict_sb3(self):
+        sd = {"lstm_actor." + k: v for k, v in self.lstm.state_dict().items()}
+        for key, m in (("mlp_extractor.policy_net.0", self.l1), ("mlp_extractor.policy_net.2", self.l2),
+                       ("action_net", self.head)):
+            sd[key + ".weight"], sd[key + ".bias"] = m.weight.detach(), m.bias.detach()
+        return sd
+
+
+def measure_stack(n, reps, hidden, layers):
+    """ha_step of a StackedRecurrentActor (stack_step_kernel) beside TorchStack, the same tensors."""
+    from cantorrl_amd.agent import StackedRecurrentActor
+    dev = "cuda:0"
+    rng = np.random.default_rng(0)
+    torch.manual_seed(0)
+    mean, var = rng.uniform(-1, 1, 13), rng.uniform(0.5, 2.0, 13)
+    ta = TorchStack(hidden, layers, mean, var)
+    actor = StackedRecurrentActor(ta.state_dict_sb3(), obs_mean=mean, obs_var=var, device=dev)
+    ta = ta.to(dev)
+    obs = torch.from_numpy(rng.uniform(-2, 2, (n, 13)).astype(np.float32)).to(dev)
+    start = torch.zeros(n, dtype=torch.uint8, device=dev)
+    out = torch.empty((n, 2), device=dev)
+    actor.reset_states(n)
+    t_kernel = median_us(lambda: actor.step(obs, start, out=out), reps)
+    st = [torch.zeros((layers, n, hidden), device=dev), torch.zeros((layers, n, hidden), device=dev)]
+
+    def torch_step():
+        _, st[0], st[1] = ta(obs, start, st[0], st[1])
+    t_torch = median_us(torch_step, reps)
+    actor.close()
+    flop = 2 * (4 * hidden * (13 + hidden) + (layers - 1) * 8 * hidden * hidden + 64 * hidden + 64 * 64 + 2 * 64)
+    weight_bytes = 4 * (4 * hidden * (14 + hidden) + (layers - 1) * 8 * hidden * hidden)
+    tf = n * flop / (t_kernel * 1e-6)
+    return dict(n_envs=n, hidden=hidden, layers=layers, ha_step_us=round(t_kernel, 2), torch_step_us=round(t_torch, 2),
+                flop_per_env_step=flop, ha_step_tflops=round(tf / 1e12, 3),
+                frac_f32_matrix_peak=round(tf / F32_MATRIX_PEAK, 4),
+                gate_weight_GBps_per_tile=round(weight_bytes / (t_kernel * 1e-6) / 1e9, 1),
+                speedup_vs_torch=round(t_torch / t_kernel, 2), reps=reps, device=torch.cuda.get_device_name(0))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("n_envs", nargs="*", type=int, default=[65536, 2])
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--hidden", type=int, choices=(128, 256, 512), help="with --layers: a StackedRecurrentActor")
+    ap.add_argument("--layers", type=int, choices=(1, 2, 3, 4))
     ap.add_argument("--out")
     a = ap.parse_args()
+    stacked = a.hidden is not None or a.layers is not None
     for n in a.n_envs:
-        line = json.dumps(measure(n, a.reps))
+        line = json.dumps(measure_stack(n, a.reps, a.hidden or 128, a.layers or 1) if stacked else measure(n, a.reps))
         print(line, flush=True)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
